@@ -8,6 +8,12 @@ range over the ranks. Each rank folds its shard to one partial on its GPU; for N
 the partials (608 B each) are gathered over RCCL and combined on rank 0's GPU.
 value = (k - 1) HomoAdd operations per step * steps / (max-over-ranks wall time).
 
+A plain run (python bench.py --gpus N --steps K --warmup W) sets up, warms up, times the K steps and
+prints the result line. --full adds everything else the bench measures or checks: the result's check
+against the oracle, the CPU baselines, the host-boundary rates, the strong-split, latency and
+config 3 / 4 lines, and the other workloads' resident-route and native-call lines. --dump-outputs DIR
+writes what the last timed step returned as DIR/<name>.npy (see dump_outputs of each workload).
+
 Launch: python bench.py [--gpus N --steps K --warmup W]. For N > 1 either under
 torch.distributed.run (one process per GPU, WORLD_SIZE = N), or directly: without WORLD_SIZE the
 process starts N ranks itself (a torch.distributed.run child, before any GPU call), relays rank
@@ -76,7 +82,7 @@ def visible_devices() -> int:
     return torch.cuda.device_count()
 
 
-def launch_ranks(n: int, backend: str) -> int:
+def launch_ranks(n: int, backend: str, argv) -> int:
     """`python bench.py --gpus N` without WORLD_SIZE: run the N ranks as one torch.distributed.run
     child (127.0.0.1 rendezvous on a free port, the same command line otherwise), relay rank 0's JSON
     line after checking it reports n_gpus == N, and return the child's exit status (non-zero when any
@@ -93,7 +99,7 @@ def launch_ranks(n: int, backend: str) -> int:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")  # dmabuf IPC only on this pool (RCCL peer buffers)
     env.setdefault("OMP_NUM_THREADS", "1")
@@ -119,7 +125,37 @@ def launch_ranks(n: int, backend: str) -> int:
     return 0
 
 
-def main():
+def int_limbs(x: int, bits: int):
+    """A big integer as float64 [ceil(bits / 32)]: its 32-bit limbs, least significant first (each exact)."""
+    import numpy as np
+    n = max(1, (bits + 31) // 32)
+    return np.frombuffer(int(x).to_bytes(4 * n, "little"), dtype="<u4").astype(np.float64)
+
+
+DUMP_CAP = 2_000_000    # elements per dumped array: 16 MB as float64, a few arrays stay far below 64 MB
+
+
+def dump_sample(arr, seed):
+    """`arr` as float64; above DUMP_CAP elements a fixed sample of them (sorted positions drawn once from
+    `seed`, the same for every run with the same arguments)."""
+    import numpy as np
+    arr = np.asarray(arr).reshape(-1)
+    if arr.size > DUMP_CAP:
+        pos = np.sort(np.random.default_rng(seed).choice(arr.size, DUMP_CAP, replace=False))
+        arr = arr[pos]
+    return arr.astype(np.float64)
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
                     help="ranks (one per GPU); default WORLD_SIZE under torch.distributed.run, else 1")
@@ -140,12 +176,22 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-e2e", action="store_true", help="sum: skip the host-boundary (PCIe/decimal) rates")
     ap.add_argument("--e2e-dec-rows", type=int, default=1_000_000, help="sum: decimal-route sample rows")
-    ap.add_argument("--verify", type=int, default=1, help="check the result on rank 0")
+    ap.add_argument("--verify", type=int, default=None,
+                    help="check the result on rank 0 (default: 1 with --full, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the result and measure everything beside the headline figure (CPU baselines, "
+                         "host-boundary rates, latency / strong-split / config 3 and 4 lines, resident-route and "
+                         "native-call lines); without it --no-cpu-baseline, --no-e2e and --no-extras are implied")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-extras", action="store_true",
                     help="sum: skip the extra lines (configs 3 and 4, latency, strong scaling, one-process multi-GPU)")
     ap.add_argument("--strong-rows", type=int, default=10_000_000,
                     help="rows of the strong-scaling and one-process multi-GPU lines (the north-star config)")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: set up, warm up, time the steps, report
+        args.no_cpu_baseline = args.no_e2e = args.no_extras = True
+    args.verify = int(args.full) if args.verify is None else args.verify
     dflt = {"sum": (10_000_000, 20, 3, 2), "product_filter": (10_000_000, 10, 5, 3),
             "encrypt_sum": (1_000_000, 2, 1, 4), "order": (10_000_000, 10, 2, 3),
             "entry_search": (10_000_000, 10, 2, 5)}[args.workload]
@@ -161,8 +207,10 @@ def main():
         args.gpus = int(env_world) if env_world else 1
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if env_world is None and args.gpus > 1:
-        return launch_ranks(args.gpus, backend)
+        return launch_ranks(args.gpus, backend, argv)
     if env_world is not None and int(env_world) != args.gpus:
         print(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={env_world}", file=sys.stderr)
         return 2
@@ -237,6 +285,8 @@ def main():
     extra = wl.extra_distributed() if not args.no_extras else {}
     out = None
     if rank == 0:
+        if args.dump_outputs:  # before report(): its --full lines run further calls on the same engine
+            write_outputs(args.dump_outputs, wl.dump_outputs(res))
         out = wl.report(res, elapsed)
         out["fill_s"] = t_fill
         if ranks_ok is not None:
@@ -390,6 +440,10 @@ class _Workload:
                             "seq_len": None, "model": None}, **extra_cfg),
         }
 
+    def dump_outputs(self, res):
+        """{name: float32/float64 array} of what the last timed step() returned to its caller."""
+        raise NotImplementedError
+
     def close(self):
         pass
 
@@ -408,6 +462,10 @@ class SumWorkload(_Workload):
 
     def step(self):
         return self.fold_or_combine(self.col, self.nsq)
+
+    def dump_outputs(self, res):
+        """sum: the fold (the SumAll ciphertext, < n^2) as 32-bit limbs."""
+        return {"sum": int_limbs(res, self.nsq.bit_length())}
 
     def report(self, res, elapsed):
         a, key, nsq = self.args, self.key, self.nsq
@@ -1004,6 +1062,27 @@ class ProductFilterWorkload(_Workload):
         out = self.common("RSA HomoMult product + OPE range filter rows/sec (2048-bit key)",
                           self.total * a.steps / elapsed, "rows/s", elapsed, "rsa_multall_plus_ope_filter_10M_2048bit",
                           {"key_bits": key["n"].bit_length(), "filters_per_step": 4})
+        if a.full:
+            self.resident_search_lines(filt, counts)
+        out.update(data="synthetic (seeded RSA ciphertexts of U[1,10^4) plaintexts, seeded OPE map)",
+                   roofline=roof, filter_roofline=filt, cpu_baseline=cpu, verified=ok,
+                   fold_ms_per_step=self.fold_ms / a.steps, filter_ms_per_step=self.filter_ms / a.steps,
+                   homomult_per_s=(self.total - 1) * a.steps / elapsed, matches=counts)
+        return out
+
+    def dump_outputs(self, res):
+        """product_filter: the MultAll product as 32-bit limbs, the four filters' match counts (gt, ge, lt,
+        le) and the row ids the last filter (le) left in the caller's device buffer."""
+        import numpy as np
+        prod, counts = res
+        ids = self.d_out[: counts["le"]].cpu().numpy().view(np.uint32)
+        return {"product": int_limbs(prod, self.key["n"].bit_length()),
+                "counts": np.array([counts[op] for op in ("gt", "ge", "lt", "le")], dtype=np.float64),
+                "le_row_ids": dump_sample(ids, self.args.seed)}
+
+    def resident_search_lines(self, filt, counts):
+        """--full: the Search routes through the resident OPE column, added to the filter roofline."""
+        import numpy as np
         # Search through the resident OPE column with host output (the JNA-shaped call: bound as text, row
         # ids back in host memory), outside the timed region
         # into the reply buffer a caller reuses (engine-allocated, dds_host_alloc: one DMA), and into a fresh
@@ -1071,11 +1150,6 @@ class ProductFilterWorkload(_Workload):
                     "stores the mask words through the buffer's device mapping and the per-tile counts into a "
                     "mapped host array the host adds up" + (": no copies" if zc else
                                                               "; DDSHE_MASK_ZEROCOPY=0: one D2H of n/8 bytes + the count")}
-        out.update(data="synthetic (seeded RSA ciphertexts of U[1,10^4) plaintexts, seeded OPE map)",
-                   roofline=roof, filter_roofline=filt, cpu_baseline=cpu, verified=ok,
-                   fold_ms_per_step=self.fold_ms / a.steps, filter_ms_per_step=self.filter_ms / a.steps,
-                   homomult_per_s=(self.total - 1) * a.steps / elapsed, matches=counts)
-        return out
 
     def native_search(self):
         """The same route from C++ (tools/native/search_bench: the call a JNA binding makes, without the
@@ -1194,6 +1268,17 @@ class EncryptSumWorkload(_Workload):
                    verified=ok, encrypt_ms_per_step=self.enc_ms / a.steps)
         return out
 
+    def dump_outputs(self, res):
+        """encrypt_sum: the sum of the fresh ciphertexts as 32-bit limbs, and 16 of the ciphertexts the
+        step left in its output column (rows drawn once from the seed), one row of limbs each."""
+        import numpy as np
+        bits = self.key["nsquare"].bit_length()
+        out = {"sum": int_limbs(res, bits)}
+        if self.mine:
+            rows = np.sort(np.random.default_rng(self.args.seed).choice(self.mine, min(16, self.mine), replace=False))
+            out["ciphertexts"] = np.stack([int_limbs(self.out.read(int(i), 1)[0], bits) for i in rows])
+        return out
+
     def close(self):
         self.rcol.close()
         self.out.close()
@@ -1269,12 +1354,18 @@ class OrderWorkload(_Workload):
                           elapsed, "ope_orderls_10M", {})
         out.update(data="synthetic (seeded OPE map of U[1,10^4) plaintexts, 5% rows lacking the position)",
                    dtype="int64", roofline=roof, cpu_baseline=cpu, verified=ok)
-        if self.world == 1:
+        if self.world == 1 and a.full:
             try:
                 out["resident_opecol_order"] = self.resident_order()
             except Exception as e:  # noqa: BLE001
                 out["resident_opecol_order"] = {"error": repr(e)}
         return out
+
+    def dump_outputs(self, res):
+        """order: this rank's OrderLS row permutation as the step left it in the caller's device buffer
+        (step() itself returns nothing)."""
+        import numpy as np
+        return {"order": dump_sample(self.d_out[: self.mine].cpu().numpy().view(np.uint32), self.args.seed)}
 
     def resident_order(self):
         """The serving form: OrderLS on the same rows as a resident OPE column (dds_opecol_order: the
@@ -1421,7 +1512,7 @@ class EntrySearchWorkload(_Workload):
         if t_or is not None and t_eq is not None:
             roof["traffic"] = (t_or + t_eq) / 2
         mut = None
-        if self.world == 1:  # before the CPU baseline (its 1.6M Python strings slow every later Python call)
+        if self.world == 1 and a.full:  # before the CPU baseline (its 1.6M Python strings slow every later Python call)
             try:
                 mut = self.mutations()
             except Exception as e:  # noqa: BLE001  (reported in the line, not lost)
@@ -1445,9 +1536,14 @@ class EntrySearchWorkload(_Workload):
                    roofline=roof, cpu_baseline=cpu, verified=ok, matches={"or": len(res[0]), "eq": len(res[1])})
         if mut is not None:
             out["resident_mutations"] = mut
-        if self.world == 1:
+        if self.world == 1 and a.full:
             out["native_call"] = self.native_scan()
         return out
+
+    def dump_outputs(self, res):
+        """entry_search: the row ids of the SearchEntryOR and of the SearchEq reply."""
+        return {"search_entry_or_rows": dump_sample(res[0], self.args.seed),
+                "search_eq_rows": dump_sample(res[1], self.args.seed)}
 
     def native_scan(self):
         """The same two routes from C++ (tools/native/scan_bench: the calls a JNA binding makes, without the

@@ -1,5 +1,5 @@
 """The committed bench lines (profiles/r01_bench_*.json and the round-2 default line, written
-by `python bench.py [--workload …]` on an MI355X) carry every field of the driver's JSON contract, with the roofline and CPU-baseline
+by `python bench.py --full [--workload …]` on an MI355X) carry every field of the driver's JSON contract, with the roofline and CPU-baseline
 objects, and a verified result. CPU-only: reads the committed files."""
 import glob
 import json

@@ -2,7 +2,7 @@
 # OrderLS dictionary codes (B: DDSHE_ORDER_DICT=1, default) against the key passes (A: 0), same box: the
 # order tests both ways, the order bench line and the skew probe per build (A B, twice), a kernel trace of B.
 export TMPDIR=/tmp
-B="python3 -u bench.py --workload order --steps 20 --no-cpu-baseline"
+B="python3 -u bench.py --full --workload order --steps 20 --no-cpu-baseline"
 P="python3 -u tools/order_skew_probe.py"
 T="python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py"
 exec tools/gpurun/steps.sh \

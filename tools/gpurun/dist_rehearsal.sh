@@ -4,7 +4,7 @@
 # combined result, or by each rank checking its own shard and a min over ranks), the headline at 4 ranks,
 # and the headline at 2 ranks with --no-extras (verification must not depend on the extras).
 export TMPDIR=/tmp
-G="env DDSHE_DIST_BACKEND=gloo python3 -u bench.py --no-cpu-baseline"
+G="env DDSHE_DIST_BACKEND=gloo python3 -u bench.py --full --no-cpu-baseline"
 exec tools/gpurun/steps.sh \
   "300 dr_sum4 $G --gpus 4 --steps 3 --warmup 1" \
   "200 dr_sum2_noextras $G --gpus 2 --steps 3 --warmup 1 --no-extras" \

@@ -3,7 +3,7 @@
 # one box: the string-table tests on the 4-load build, the entry_search line per build (twice), traces.
 export TMPDIR=/tmp
 L=tools/abtest/libs
-B="python3 -u bench.py --workload entry_search --no-cpu-baseline --steps 20"
+B="python3 -u bench.py --full --workload entry_search --no-cpu-baseline --steps 20"
 exec tools/gpurun/steps.sh \
   "300 oc_t env DDSHE_LIB=$L/libddshe_fp4.so python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_strtab.py tests/test_gpu_strscan.py tests/test_gpu_mutations.py" \
   "300 oc_2a env DDSHE_LIB=$L/libddshe_fp2.so $B" "300 oc_4a env DDSHE_LIB=$L/libddshe_fp4.so $B" "300 oc_8a env DDSHE_LIB=$L/libddshe_fp8.so $B" \

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OCC2=tools/abtest/libs/libddshe_occ2.so
 exec tools/gpurun/steps.sh \
   "300 lad_tests python -u -m pytest tests/test_gpu_encrypt.py -x -q --timeout 200 --timeout-method thread" \
-  "200 lad_occ2_a env DDSHE_LIB=$OCC2 python -u bench.py --workload encrypt_sum --no-cpu-baseline --steps 2 --warmup 1" \
-  "200 lad_occ3_a python -u bench.py --workload encrypt_sum --no-cpu-baseline --steps 2 --warmup 1" \
-  "200 lad_occ2_b env DDSHE_LIB=$OCC2 python -u bench.py --workload encrypt_sum --no-cpu-baseline --steps 2 --warmup 1" \
-  "200 lad_occ3_b python -u bench.py --workload encrypt_sum --no-cpu-baseline --steps 2 --warmup 1"
+  "200 lad_occ2_a env DDSHE_LIB=$OCC2 python -u bench.py --full --workload encrypt_sum --no-cpu-baseline --steps 2 --warmup 1" \
+  "200 lad_occ3_a python -u bench.py --full --workload encrypt_sum --no-cpu-baseline --steps 2 --warmup 1" \
+  "200 lad_occ2_b env DDSHE_LIB=$OCC2 python -u bench.py --full --workload encrypt_sum --no-cpu-baseline --steps 2 --warmup 1" \
+  "200 lad_occ3_b python -u bench.py --full --workload encrypt_sum --no-cpu-baseline --steps 2 --warmup 1"

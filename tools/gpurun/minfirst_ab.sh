@@ -3,8 +3,8 @@
 # (DDSHE_ORDER_MINFIRST=1, default) against the first row's key (0), one box: order tests under both, the
 # order line and the skew probe alternating, kernel traces under both.
 export TMPDIR=/tmp
-B="python3 -u bench.py --workload order --steps 20 --no-cpu-baseline"
-K="python3 -u bench.py --workload order --steps 10 --no-cpu-baseline"
+B="python3 -u bench.py --full --workload order --steps 20 --no-cpu-baseline"
+K="python3 -u bench.py --full --workload order --steps 10 --no-cpu-baseline"
 exec tools/gpurun/steps.sh \
   "300 mf_t1 python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py tests/test_gpu_mutations.py" \
   "300 mf_t0 env DDSHE_ORDER_MINFIRST=0 python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py" \

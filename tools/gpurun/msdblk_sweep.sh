@@ -4,7 +4,7 @@
 # build, then the order line (twice) and the skew probe per build, a trace per build.
 export TMPDIR=/tmp
 L=tools/abtest/libs
-B="python3 -u bench.py --workload order --steps 20 --no-cpu-baseline"
+B="python3 -u bench.py --full --workload order --steps 20 --no-cpu-baseline"
 P="python3 -u tools/order_skew_probe.py"
 T="python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py"
 S=()

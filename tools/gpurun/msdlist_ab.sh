@@ -12,7 +12,7 @@
 # 2,048 rows / list + memory rounds: no faster than A, the list kernel 7.4 us.)
 export TMPDIR=/tmp
 L=tools/abtest/libs
-B="python3 -u bench.py --workload order --steps 20 --no-cpu-baseline"
+B="python3 -u bench.py --full --workload order --steps 20 --no-cpu-baseline"
 P="python3 -u tools/order_skew_probe.py"
 T="python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py"
 exec tools/gpurun/steps.sh \

@@ -6,7 +6,7 @@
 # against 16.3 for one entry per block by the global index: segments of > 12 entries serialise.)
 export TMPDIR=/tmp
 L=tools/abtest/libs
-B="python3 -u bench.py --workload order --steps 20 --no-cpu-baseline"
+B="python3 -u bench.py --full --workload order --steps 20 --no-cpu-baseline"
 P="python3 -u tools/order_skew_probe.py"
 T="python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py"
 A="env DDSHE_LIB=$L/libddshe_swar4.so"

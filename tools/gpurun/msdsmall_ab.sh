@@ -5,7 +5,7 @@
 # every bucket small and multi-key) and the order line per build (A B C, twice), a trace of C.
 export TMPDIR=/tmp
 L=tools/abtest/libs
-B="python3 -u bench.py --workload order --steps 20 --no-cpu-baseline"
+B="python3 -u bench.py --full --workload order --steps 20 --no-cpu-baseline"
 P="python3 -u tools/order_skew_probe.py"
 T="python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py"
 A="env DDSHE_LIB=$L/libddshe_swar4.so"

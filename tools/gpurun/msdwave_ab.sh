@@ -3,7 +3,7 @@
 # round 5), same box: order tests under both, the skew probe (bench column, uniform 54-bit keys: every
 # bucket multi-key, three keys) and the order line, alternating.
 export TMPDIR=/tmp
-B="python3 -u bench.py --workload order --steps 20 --no-cpu-baseline"
+B="python3 -u bench.py --full --workload order --steps 20 --no-cpu-baseline"
 exec tools/gpurun/steps.sh \
   "300 mw_t8 python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py" \
   "300 mw_t64 env DDSHE_ORDER_MSDWAVE=64 python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_order.py" \

@@ -7,7 +7,7 @@ P=gpurun_out/prof
 specs=()
 for v in "$@"; do
   name=${v%%:*}; envs=${v#*:}
-  specs+=("240 bench_$name $envs python3 -u bench.py --workload order --no-cpu-baseline --steps 10")
-  specs+=("240 ks_$name $envs rocprofv3 --kernel-trace --stats --output-format csv -d $P/order_$name -o run -- python3 bench.py --workload order --no-cpu-baseline --steps 5 --verify 0")
+  specs+=("240 bench_$name $envs python3 -u bench.py --full --workload order --no-cpu-baseline --steps 10")
+  specs+=("240 ks_$name $envs rocprofv3 --kernel-trace --stats --output-format csv -d $P/order_$name -o run -- python3 bench.py --full --workload order --no-cpu-baseline --steps 5 --verify 0")
 done
 exec tools/gpurun/steps.sh "${specs[@]}"

@@ -5,7 +5,7 @@
 # cuts them per call).
 export TMPDIR=/tmp
 P=gpurun_out/prof6
-B="python3 -u bench.py --workload order --no-cpu-baseline"
+B="python3 -u bench.py --full --workload order --no-cpu-baseline"
 exec tools/gpurun/steps.sh \
   "300 oc_tests python -u -m pytest tests/test_gpu_order.py -x -q --timeout 200 --timeout-method thread" \
   "150 oc_0a env DDSHE_ORDER_CARRY=0 $B --steps 20" \

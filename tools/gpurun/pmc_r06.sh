@@ -5,8 +5,8 @@
 # (tools/abtest/libs/libddshe_swar4t.so) against the in-tree non-temporal ones (A B A B).
 export TMPDIR=/tmp
 P=gpurun_out/prof6
-B="python3 bench.py --no-cpu-baseline --no-e2e"
-E="python3 -u bench.py --workload entry_search --no-cpu-baseline --steps 20"
+B="python3 bench.py --full --no-cpu-baseline --no-e2e"
+E="python3 -u bench.py --full --workload entry_search --no-cpu-baseline --steps 20"
 L=tools/abtest/libs
 S=()
 for w in sum:--no-extras pf:"--workload product_filter" es:"--workload entry_search" order:"--workload order" enc:"--workload encrypt_sum"; do

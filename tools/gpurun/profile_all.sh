@@ -5,10 +5,10 @@
 # Outputs under gpurun_out/prof/<name>/ (CSV); copy the summaries to be judged into profiles/.
 export TMPDIR=/tmp
 P=gpurun_out/prof
-B="python3 bench.py --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --no-cpu-baseline --no-e2e"
 exec tools/gpurun/steps.sh \
   "300 ks_sum rocprofv3 --kernel-trace --stats --output-format csv -d $P/sum -o run -- $B --steps 5" \
-  "300 ks_e2e rocprofv3 --kernel-trace --stats --output-format csv -d $P/e2e -o run -- python3 bench.py --no-cpu-baseline --no-extras --steps 1" \
+  "300 ks_e2e rocprofv3 --kernel-trace --stats --output-format csv -d $P/e2e -o run -- python3 bench.py --full --no-cpu-baseline --no-extras --steps 1" \
   "300 ks_pf rocprofv3 --kernel-trace --stats --output-format csv -d $P/product_filter -o run -- $B --workload product_filter --steps 5" \
   "400 ks_enc rocprofv3 --kernel-trace --stats --output-format csv -d $P/encrypt_sum -o run -- $B --workload encrypt_sum --steps 1 --warmup 1" \
   "300 ks_order rocprofv3 --kernel-trace --stats --output-format csv -d $P/order -o run -- $B --workload order --steps 5" \

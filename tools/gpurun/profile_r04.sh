@@ -7,7 +7,7 @@
 # Outputs under gpurun_out/prof/<name>/ (CSV); the summaries to be judged are copied into profiles/.
 export TMPDIR=/tmp
 P=gpurun_out/prof
-B="python3 bench.py --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --no-cpu-baseline --no-e2e"
 exec tools/gpurun/steps.sh \
   "300 ks_sum rocprofv3 --kernel-trace --stats --output-format csv -d $P/sum -o run -- $B --no-extras --verify 0 --steps 5" \
   "300 ks_order rocprofv3 --kernel-trace --stats --output-format csv -d $P/order -o run -- $B --workload order --steps 5" \

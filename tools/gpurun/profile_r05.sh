@@ -9,7 +9,7 @@
 # profiles/ summaries.
 export TMPDIR=/tmp
 P=gpurun_out/prof
-B="python3 bench.py --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --no-cpu-baseline --no-e2e"
 # PART=ks: the kernel-stats runs only; PART=pmc: the PMC passes only (each fits one gpurun call)
 KS=(
   "300 ks_sum rocprofv3 --kernel-trace --stats --output-format csv -d $P/sum -o run -- $B --no-extras --verify 0 --steps 5"

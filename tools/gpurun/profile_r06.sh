@@ -9,7 +9,7 @@
 # Summaries: tools/dispatch_stats.py, tools/pmc_valu_summary.py -> profiles/r06_*.
 export TMPDIR=/tmp
 P=gpurun_out/prof6
-B="python3 bench.py --no-cpu-baseline --no-e2e"
+B="python3 bench.py --full --no-cpu-baseline --no-e2e"
 V="SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU_INT64 SQ_INSTS_VALU_INT32 GRBM_GUI_ACTIVE"
 KS=(
   "300 order_keys2_0 env DDSHE_ORDER_KEYS2=0 python -u -m pytest tests/test_gpu_order.py -x -q --timeout 200 --timeout-method thread"

@@ -4,7 +4,7 @@
 # line per build (A B A B), a trace of the in-tree build.
 export TMPDIR=/tmp
 L=tools/abtest/libs
-B="python3 -u bench.py --workload entry_search --no-cpu-baseline --steps 20"
+B="python3 -u bench.py --full --workload entry_search --no-cpu-baseline --steps 20"
 exec tools/gpurun/steps.sh \
   "300 sw_t python3 -u -m pytest -x -q --timeout 250 --timeout-method thread tests/test_gpu_strtab.py tests/test_gpu_strscan.py tests/test_gpu_mutations.py tests/test_gpu_routes.py" \
   "300 sw_1a env DDSHE_LIB=$L/libddshe_fp4.so $B" "300 sw_1b $B" \
