@@ -2046,10 +2046,29 @@ int encrypt_device(Worker* w, hipStream_t st, ModConsts& mc, const bn::Limbs& n,
 
 // CRT form of a Paillier key (p, q): per-modulus constants of p^2, q^2, n^2 and the Garner
 // constants c1R = (q^2)^-1 R_p, c2R = -(q^2)^-1 R_p (mod p^2), q2R = q^2 R_n (mod n^2).
+// Decryption constants of one (p, q, g) (decrypt_crt_device), built on the first decrypt with that g, so
+// encrypt-only users pay nothing. For factor i of (p, q), at d + off[i], in the limbs of its square's shape:
+//   2^(j W_n)·R_d | R_d (mod d^2): x_d = c mod d^2 from the halves of c split at limb j of the n^2 layout
+//   h_d·R_d | d^2 - h_d, with h_d = L_d(g^(d-1) mod d^2)^-1 mod d
+//   d^-1 mod 2^(sdiv W_d), sdiv = ceil((bits(d) + 1) / W_d) limbs (the exact division by d)
+// (S_d limbs each, d the factor); then, at d + off_e, e_p·R_n | e_q·R_n (mod n) in the limbs of n's shape.
+struct DecKey {
+  std::shared_ptr<ModConsts> mnn;  // modulus n: the recombination and the plaintexts' layout
+  bn::Limbs e[2];                  // p - 1, q - 1
+  int j = 0, sdiv[2] = {0, 0};
+  size_t off[2] = {0, 0}, off_e = 0;
+  uint32_t* d = nullptr;
+  ~DecKey() {
+    if (d) (void)hipFree(d);
+  }
+};
+
 struct CrtKey {
   std::shared_ptr<ModConsts> mp, mq, mn;
-  bn::Limbs n;
+  bn::Limbs n, p, q;
   uint32_t* d = nullptr;  // c1R | c2R (2 Sp limbs) | q2R (Sn limbs)
+  std::mutex dmu;
+  std::map<bn::Limbs, std::shared_ptr<DecKey>> dec;  // by g: two keys over the same p, q do not share h_d
   ~CrtKey() {
     if (d) (void)hipFree(d);
   }
@@ -2070,6 +2089,8 @@ int get_crt_key(dds_ctx* ctx, const bn::Limbs& p, const bn::Limbs& q, std::share
     return fail(DDS_E_ARG, "p, q must be distinct odd primes");
   auto k = std::make_shared<CrtKey>();
   k->n = bn::mul(p, q);
+  k->p = p;
+  k->q = q;
   const bn::Limbs p2 = bn::mul(p, p), q2 = bn::mul(q, q), n2 = bn::mul(k->n, k->n);
   auto be = [](const bn::Limbs& v) {
     std::vector<uint8_t> b(bn::byte_length(v));
@@ -2143,6 +2164,184 @@ int encrypt_crt_device(Worker* w, hipStream_t st, CrtKey& k, const bn::Limbs& g,
   uint32_t flags = 0;
   HIP_TRY(read_sync(w, st, fl, &flags, 4));
   if (flags) return fail(DDS_E_RANGE, "r does not fit below 2^bits(n)");
+  return DDS_OK;
+}
+
+// N^-1 mod 2^k for an odd N (Newton: inv <- inv (2 - N inv) doubles the correct low bits)
+void inv_mod_pow2(const bn::Limbs& N, size_t k, bn::Limbs* out) {
+  bn::Limbs& inv = *out;
+  inv = bn::Limbs{1};
+  const bn::Limbs two{2};
+  for (size_t ok = 1; ok < k; ok *= 2) {
+    const bn::Limbs t = low_bits(bn::mul(N, inv), k);
+    inv = low_bits(bn::mul(inv, low_bits(bn::sub(bn::add(bn::pow2(k), two), t), k)), k);
+  }
+  bn::trim(inv);
+}
+
+int get_dec_key(dds_ctx* ctx, CrtKey& k, const bn::Limbs& g, std::shared_ptr<DecKey>* out) {
+  {
+    std::lock_guard<std::mutex> lk(k.dmu);
+    auto it = k.dec.find(g);
+    if (it != k.dec.end()) {
+      *out = it->second;
+      return DDS_OK;
+    }
+  }
+  auto dk = std::make_shared<DecKey>();
+  const ModConsts& mn = *k.mn;
+  // Shape check (as crt_fits for encrypt): c, a row of the n^2 layout below 2 n^2, splits at limb j into
+  // c_lo (j W_n bits) and c_hi; both must fit the limbs of p^2 and of q^2 with the usual 2 bits to spare
+  const size_t cbits = mn.bits + 1;
+  dk->j = (int)((cbits + 2 * (size_t)mn.W - 1) / (2 * (size_t)mn.W));
+  const size_t lo = (size_t)dk->j * mn.W, hi = cbits > lo ? cbits - lo : 0;
+  for (const ModConsts* md : {k.mp.get(), k.mq.get()}) {
+    const size_t cap = (size_t)md->S * md->W - 2;
+    if (dk->j < 1 || dk->j >= mn.S || lo > cap || hi > cap)
+      return fail(DDS_E_ARG, "factors too unbalanced for CRT decrypt");
+  }
+  int rc;
+  {
+    std::vector<uint8_t> nb(bn::byte_length(k.n));
+    bn::to_be(k.n, nb.data(), nb.size());
+    if ((rc = get_mod(ctx, nb.data(), nb.size(), &dk->mnn))) return rc;
+  }
+  const ModConsts& mnn = *dk->mnn;
+  const bn::Limbs one{1}, two{2};
+  std::vector<uint32_t> host;
+  auto put = [&](const std::vector<uint32_t>& v) { host.insert(host.end(), v.begin(), v.end()); };
+  const bn::Limbs* ds[2] = {&k.p, &k.q};
+  const ModConsts* mds[2] = {k.mp.get(), k.mq.get()};
+  for (int i = 0; i < 2; ++i) {
+    const bn::Limbs& d = *ds[i];
+    const ModConsts& md = *mds[i];
+    const bn::Limbs& d2 = md.N;
+    dk->e[i] = bn::sub(d, one);
+    dk->off[i] = host.size();
+    put(md.rw(bn::mulmod(bn::mod(bn::pow2(lo), d2), md.Rmod, d2)));
+    put(md.rw(md.Rmod));
+    // h_d = L_d(g^(d-1) mod d^2)^-1 mod d, by Euler (d prime; verified below)
+    const bn::Limbs v = bn::powmod(bn::mod(g, d2), dk->e[i], d2);
+    if (v.empty()) return fail(DDS_E_ARG, "g is not coprime to n");
+    bn::Limbs l;
+    if (!bn::mod(bn::sub(v, one), d, &l).empty()) return fail(DDS_E_ARG, "p, q must be distinct primes");
+    l = bn::mod(l, d);
+    const bn::Limbs h = bn::powmod(l, bn::sub(d, two), d);
+    if (bn::cmp(bn::mulmod(h, l, d), one) != 0) return fail(DDS_E_ARG, "L(g^(d-1) mod d^2) is not invertible mod d");
+    put(md.rw(bn::mulmod(h, md.Rmod, d2)));
+    put(md.rw(bn::sub(d2, h)));
+    dk->sdiv[i] = (int)((bn::bit_length(d) + 1 + md.W - 1) / md.W);
+    if (dk->sdiv[i] > md.S) return fail(DDS_E_UNSUPPORTED, "factor too wide for its shape");
+    bn::Limbs dinv;
+    inv_mod_pow2(d, (size_t)dk->sdiv[i] * md.W, &dinv);
+    put(bn::to_rw(dinv, md.S, md.W));
+  }
+  dk->off_e = host.size();
+  for (int i = 0; i < 2; ++i) {  // e_p = q (q^-1 mod p), e_q = p (p^-1 mod q)
+    const bn::Limbs &d = *ds[i], &o = *ds[1 - i];
+    const bn::Limbs oi = bn::powmod(bn::mod(o, d), bn::sub(d, two), d);
+    if (bn::cmp(bn::mulmod(oi, o, d), one) != 0) return fail(DDS_E_ARG, "p, q must be distinct primes");
+    put(mnn.rw(bn::mulmod(bn::mul(o, oi), mnn.Rmod, k.n)));
+  }
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&dk->d, host.size() * 4) != hipSuccess)
+    return fail(DDS_E_NOMEM, "decrypt const alloc");
+  HIP_TRY(hipMemcpy(dk->d, host.data(), host.size() * 4, hipMemcpyHostToDevice));
+  std::lock_guard<std::mutex> lk(k.dmu);
+  auto it = k.dec.find(g);
+  if (it != k.dec.end()) {
+    *out = it->second;
+    return DDS_OK;
+  }
+  if (k.dec.size() > 8) k.dec.clear();
+  k.dec.emplace(g, dk);
+  *out = dk;
+  return DDS_OK;
+}
+
+// out[i] = HomoAdd.decrypt(c_i) for rows of c (n^2 layout, values < 2 n^2), big-endian, n_bytes each, through
+// the CRT halves (formulas at k_lfun_w). Chunks of at most 2^18 rows: 2048 workgroups of 128 rows still fill
+// the chip, at a quarter of the encrypt path's scratch. A row not coprime to n fails the call (DDS_E_RANGE).
+// With timing on (dds_ctx_set_timing) the kernels' device time goes to total_ms and the ladders' to fold_ms.
+int decrypt_crt_device(dds_ctx* ctx, Worker* w, hipStream_t st, CrtKey& k, DecKey& dk, const uint32_t* d_c,
+                       size_t cstride, size_t count, uint8_t* out, size_t n_bytes) {
+  ModConsts &mn = *k.mn, &mnn = *dk.mnn;
+  ModConsts* mds[2] = {k.mp.get(), k.mq.get()};
+  const size_t chunk = std::min<size_t>(round_up(count, 64), (size_t)1 << 18);
+  const size_t sh = (size_t)std::max(mds[0]->S, mds[1]->S) * chunk * 4, sn = (size_t)mnn.S * chunk * 4;
+  const size_t sizes[6] = {sh, sh, sh, sn, sn, sn};
+  for (int i = 0; i < 6; ++i) HIP_TRY(w->crt[i].ensure(sizes[i]));
+  HIP_TRY(w->flags.ensure(16));
+  uint32_t* fl = w->flags.as<uint32_t>() + 1;
+  HIP_TRY(hipMemsetAsync(fl, 0, 4, st));
+  uint32_t *A = w->crt[0].as<uint32_t>(), *B = w->crt[1].as<uint32_t>(), *C = w->crt[2].as<uint32_t>(),
+           *H = w->crt[5].as<uint32_t>();
+  const bool timed = ctx->timing.load();
+  float ladder_ms = 0, kernel_ms = 0;
+  uint64_t ladders = 0;
+  const bool dev_egress = mnn.S <= kEgressMaxLimbs;
+  std::vector<uint32_t> hh, limbs;
+  int rc;
+  for (size_t c0 = 0; c0 < count; c0 += chunk) {
+    const size_t cc = std::min(chunk, count - c0);
+    if (timed) HIP_TRY(hipEventRecord(w->ev[2], st));
+    for (int i = 0; i < 2; ++i) {
+      ModConsts& md = *mds[i];
+      const int S = md.S;
+      const uint32_t* kc = dk.d + dk.off[i];
+      uint32_t* Mn = w->crt[3 + i].as<uint32_t>();
+      HIP_TRY(launch_repack(d_c + (size_t)dk.j * cstride + c0, cstride, mn.S - dk.j, mn.W, A, chunk, S, md.W, cc, fl, st));
+      HIP_TRY(launch_repack(d_c + c0, cstride, dk.j, mn.W, B, chunk, S, md.W, cc, fl, st));
+      HIP_TRY(launch_crt_h(S, A, B, chunk, cc, md.d, kc, md.n0, C, st));  // x_d = c mod d^2
+      if (timed) HIP_TRY(hipEventRecord(w->ev[0], st));
+      if ((rc = modexp_device(w, st, md, dk.e[i], nullptr, C, chunk, nullptr, cc, A, chunk))) return rc;  // u_d
+      if (timed) {
+        float ms = 0;
+        HIP_TRY(hipEventRecord(w->ev[1], st));
+        HIP_TRY(hipEventSynchronize(w->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+        ladder_ms += ms;
+        ++ladders;
+      }
+      HIP_TRY(launch_lfun_w(S, A, chunk, cc, md.d, kc + 2 * (size_t)S, md.n0, B, st));
+      HIP_TRY(launch_lfun_div(B, A, chunk, S, dk.sdiv[i], md.W, kc + 4 * (size_t)S, C, cc, fl, st));
+      HIP_TRY(launch_repack(C, chunk, dk.sdiv[i], md.W, Mn, chunk, mnn.S, mnn.W, cc, fl, st));
+    }
+    HIP_TRY(launch_crt_h(mnn.S, w->crt[3].as<uint32_t>(), w->crt[4].as<uint32_t>(), chunk, cc, mnn.d, dk.d + dk.off_e,
+                         mnn.n0, H, st));
+    if (dev_egress) {
+      HIP_TRY(w->misc.ensure(cc * n_bytes));
+      HIP_TRY(launch_egress_be(H, chunk, cc, mnn.S, mnn.W, nullptr, n_bytes, w->misc.as<uint8_t>(), st));
+      if (timed) HIP_TRY(hipEventRecord(w->ev[3], st));
+      HIP_TRY(hipMemcpyAsync(out + c0 * n_bytes, w->misc.p, cc * n_bytes, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    } else {
+      hh.resize((size_t)mnn.S * chunk);
+      limbs.resize((size_t)mnn.S);
+      if (timed) HIP_TRY(hipEventRecord(w->ev[3], st));
+      HIP_TRY(hipMemcpyAsync(hh.data(), H, hh.size() * 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      for (size_t r = 0; r < cc; ++r) {
+        for (int l = 0; l < mnn.S; ++l) limbs[(size_t)l] = hh[(size_t)l * chunk + r];
+        if (!bn::to_be(mnn.value(limbs.data()), out + (c0 + r) * n_bytes, n_bytes))
+          return fail(DDS_E_RANGE, "result does not fit");
+      }
+    }
+    if (timed) {  // the chunk's kernels, first repack to egress (the copy to the host is not counted)
+      float ms = 0;
+      HIP_TRY(hipEventElapsedTime(&ms, w->ev[2], w->ev[3]));
+      kernel_ms += ms;
+    }
+  }
+  uint32_t flags = 0;
+  HIP_TRY(read_sync(w, st, fl, &flags, 4));
+  if (timed) {
+    std::lock_guard<std::mutex> lk(ctx->tmu);
+    ctx->total_ms += kernel_ms;
+    ctx->fold_ms += ladder_ms;
+    ctx->fold_launches += ladders;
+  }
+  if (flags & 2u) return fail(DDS_E_RANGE, "ciphertext not coprime to n");
+  if (flags & 1u) return fail(DDS_E_RANGE, "ciphertext does not fit the CRT halves");
   return DDS_OK;
 }
 }  // namespace
@@ -2437,6 +2636,58 @@ int dds_col_encrypt_paillier(dds_col* out, dds_col* rcol, size_t r_first, const 
     if (rc) return rc;
     out->count += count;
     return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_paillier_decrypt_batch_crt(dds_ctx* ctx, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be,
+                                   size_t q_bytes, const uint8_t* g_be, size_t g_bytes, const uint8_t* c_be,
+                                   size_t width, size_t count, uint8_t* out, size_t n_bytes) {
+  try {
+    if (!ctx || !p_be || !q_be || !g_be || (count && (!c_be || !out || width == 0))) return fail(DDS_E_ARG, "bad args");
+    if (count == 0) return DDS_OK;
+    std::shared_ptr<CrtKey> k;
+    int rc = get_crt_key(ctx, bn::from_be(p_be, p_bytes), bn::from_be(q_be, q_bytes), &k);
+    if (rc) return rc;
+    if (n_bytes < bn::byte_length(k->n)) return fail(DDS_E_BUFSIZE, "n_bytes too small");
+    std::shared_ptr<DecKey> dk;
+    if ((rc = get_dec_key(ctx, *k, bn::from_be(g_be, g_bytes), &dk))) return rc;
+    ModConsts& mn = *k->mn;
+    for (size_t i = 0; i < count; ++i)
+      if (bn::cmp(bn::from_be(c_be + i * width, width), mn.N) >= 0) return fail(DDS_E_RANGE, "c must be in [0, n^2)");
+    if ((rc = check_rows(mn, count))) return rc;
+    WorkerLease wl(ctx);
+    if ((rc = wl.acquire())) return rc;
+    Worker* w = wl.w;
+    const size_t stride = round_up(count, 64);
+    HIP_TRY(w->x.ensure((size_t)mn.S * stride * 4));
+    if ((rc = ingest(ctx, w, wl.st, mn, c_be, width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
+    return decrypt_crt_device(ctx, w, wl.st, *k, *dk, w->x.as<uint32_t>(), stride, count, out, n_bytes);
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_decrypt_paillier(dds_col* col, size_t first, size_t count, const uint8_t* p_be, size_t p_bytes,
+                             const uint8_t* q_be, size_t q_bytes, const uint8_t* g_be, size_t g_bytes, uint8_t* out,
+                             size_t n_bytes) {
+  try {
+    if (!col || !p_be || !q_be || !g_be || (count && !out)) return fail(DDS_E_ARG, "bad args");
+    std::shared_lock<std::shared_mutex> lk(col->mu);
+    if (first + count > col->count) return fail(DDS_E_ARG, "rows out of range");
+    if (count == 0) return DDS_OK;
+    std::shared_ptr<CrtKey> k;
+    int rc = get_crt_key(col->ctx, bn::from_be(p_be, p_bytes), bn::from_be(q_be, q_bytes), &k);
+    if (rc) return rc;
+    if (bn::cmp(k->mn->N, col->mc->N) != 0) return fail(DDS_E_ARG, "column modulus is not (p*q)^2");
+    if (col->mc->S != k->mn->S || col->mc->W != k->mn->W) return fail(DDS_E_UNSUPPORTED, "column limb layout");
+    if (n_bytes < bn::byte_length(k->n)) return fail(DDS_E_BUFSIZE, "n_bytes too small");
+    std::shared_ptr<DecKey> dk;
+    if ((rc = get_dec_key(col->ctx, *k, bn::from_be(g_be, g_bytes), &dk))) return rc;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    return decrypt_crt_device(col->ctx, wl.w, wl.st, *k, *dk, col->d + first, col->stride, count, out, n_bytes);
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");
   }

@@ -538,6 +538,64 @@ __global__ void __launch_bounds__(256, 2) k_crt_out(const uint32_t* __restrict__
   g.store_col(a, O, ostride, grp);
 }
 
+// ------------------------------------------------------------------------------
+// CRT Paillier decryption (HomoAdd.decrypt, SJHomoLibProvider.scala:68). For d in {p, q}:
+//   x_d = c mod d^2                      (k_crt_h over the two halves of c, see decrypt_crt_device)
+//   u_d = x_d^(d-1) mod d^2              (the modexp ladder)
+//   w_d = (u_d·h_d - h_d) mod d^2        (k_lfun_w; h_d = L_d(g^(d-1) mod d^2)^-1 mod d, L_d(u) = (u-1)/d)
+//       = d·m_d with m_d = L_d(u_d)·h_d mod d, so no arithmetic mod d is needed
+//   m_d = w_d / d, exact                 (k_lfun_div)
+// then m = (m_p·e_p + m_q·e_q) mod n (k_crt_h again, e_p = q·(q^-1 mod p), e_q = p·(p^-1 mod q)).
+// ------------------------------------------------------------------------------
+// w = canon(canon(MonPro(u, h·R)) + (d^2 - h)); hc = h·R mod d^2 | d^2 - h (2 S limbs)
+template <int S, int TPI, int W>
+__global__ void __launch_bounds__(256, 2) k_lfun_w(const uint32_t* __restrict__ U, size_t stride, size_t count,
+                                                const uint32_t* __restrict__ consts,
+                                                const uint32_t* __restrict__ hc, uint32_t n0,
+                                                uint32_t* __restrict__ Wo) {
+  using G = Grp<S, TPI, W>;
+  using M = Mont<S, TPI, W>;
+  constexpr int L = G::L;
+  G g;
+  const size_t grp = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / TPI;
+  if (grp >= count) return;
+  uint32_t n[L], u[L];
+  g.load_vec(n, consts + kConstN * S);
+  g.load_col(u, U, stride, grp);
+  M::mul_col(u, n, hc, 1, 0, n0, g.top, g.bottom);
+  g.canon(u, n);
+  {
+    uint32_t c[L];
+    g.load_vec(c, hc + S);
+#pragma unroll
+    for (int l = 0; l < L; ++l) u[l] += c[l];  // < 2 d^2, limbs < 2^(W+1)
+  }
+  g.canon(u, n);
+  g.store_col(u, Wo, stride, grp);
+}
+
+// m = w / d for w an exact multiple of d, m < 2^(Sdiv·W): m = w · d^-1 mod 2^(Sdiv·W), the low half of a
+// product (dinv: the 2-adic inverse, Sdiv limbs of W bits, wave-uniform). One row per thread, like
+// k_repack. Column j sums at most Sdiv terms below 2^(2W) onto a carry below 2^(64-W): no 64-bit overflow
+// while Sdiv <= 2^(63-2W) (128 limbs at W = 28, 512 at W = 27; the launcher checks).
+// flags[0] |= 2 for a row whose u (S limbs) is zero: c shares a factor with n.
+__global__ void k_lfun_div(const uint32_t* __restrict__ Wd, const uint32_t* __restrict__ U, size_t stride, int S,
+                           int Sdiv, int W, const uint32_t* __restrict__ dinv, uint32_t* __restrict__ Mo,
+                           size_t count, uint32_t* __restrict__ flags) {
+  const size_t row = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= count) return;
+  const uint32_t mask = (1u << W) - 1u;
+  uint64_t acc = 0;
+  for (int j = 0; j < Sdiv; ++j) {
+    for (int i = 0; i <= j; ++i) acc += (uint64_t)Wd[(size_t)i * stride + row] * dinv[j - i];
+    Mo[(size_t)j * stride + row] = (uint32_t)acc & mask;
+    acc >>= W;
+  }
+  uint32_t any = 0;
+  for (int l = 0; l < S; ++l) any |= U[(size_t)l * stride + row];
+  if (any == 0) atomicOr(flags, 2u);
+}
+
 // seeded r column (bench / tests): limb l of row i = splitmix64(splitmix64(seed ^ (row0+i)) + l),
 // truncated to `bits` bits (r < 2^bits), lowest bit forced to 1 (r != 0)
 __global__ void k_fill_random(uint32_t* __restrict__ X, size_t stride, int S, int W, uint64_t seed, uint64_t row0,
@@ -1401,6 +1459,23 @@ hipError_t launch_crt_out(int S, const uint32_t* Hn, const uint32_t* Yqn, size_t
   if (count == 0) return hipSuccess;
   DDSHE_SWITCH(S, hipLaunchKernelGGL((k_crt_out<S, TPI, W>), dim3(grid_for(count * TPI)), dim3(256), 0, st, Hn, Yqn,
                                      stride, count, consts, q2R, n0, O, ostride));
+  return hipGetLastError();
+}
+
+hipError_t launch_lfun_w(int S, const uint32_t* U, size_t stride, size_t count, const uint32_t* consts,
+                         const uint32_t* hc, uint32_t n0, uint32_t* Wo, hipStream_t st) {
+  if (count == 0) return hipSuccess;
+  DDSHE_SWITCH(S, hipLaunchKernelGGL((k_lfun_w<S, TPI, W>), dim3(grid_for(count * TPI)), dim3(256), 0, st, U, stride,
+                                     count, consts, hc, n0, Wo));
+  return hipGetLastError();
+}
+
+hipError_t launch_lfun_div(const uint32_t* Wd, const uint32_t* U, size_t stride, int S, int Sdiv, int W,
+                           const uint32_t* dinv, uint32_t* Mo, size_t count, uint32_t* flags, hipStream_t st) {
+  if (count == 0) return hipSuccess;
+  if (W < 1 || W > 28 || Sdiv < 1 || Sdiv > S || Sdiv > (1 << (63 - 2 * W))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_lfun_div, dim3(grid_for(count)), dim3(256), 0, st, Wd, U, stride, S, Sdiv, W, dinv, Mo, count,
+                     flags);
   return hipGetLastError();
 }
 

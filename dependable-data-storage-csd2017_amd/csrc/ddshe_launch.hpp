@@ -105,6 +105,12 @@ hipError_t launch_crt_h(int S, const uint32_t* Yp, const uint32_t* Yq, size_t st
 hipError_t launch_crt_out(int S, const uint32_t* Hn, const uint32_t* Yqn, size_t stride, size_t count,
                           const uint32_t* consts, const uint32_t* q2R, uint32_t n0, uint32_t* O, size_t ostride,
                           hipStream_t st);
+// CRT decryption pieces (see ddshe_kernels.hip): w = (u·h - h) mod d^2 (hc = h·R | d^2 - h, 2*S limbs), and
+// the exact division m = w / d as w · dinv mod 2^(Sdiv·W) (Sdiv limbs out; flags[0] |= 2 for a row with u == 0)
+hipError_t launch_lfun_w(int S, const uint32_t* U, size_t stride, size_t count, const uint32_t* consts,
+                         const uint32_t* hc, uint32_t n0, uint32_t* Wo, hipStream_t st);
+hipError_t launch_lfun_div(const uint32_t* Wd, const uint32_t* U, size_t stride, int S, int Sdiv, int W,
+                           const uint32_t* dinv, uint32_t* Mo, size_t count, uint32_t* flags, hipStream_t st);
 hipError_t launch_fill_random(uint32_t* X, size_t stride, int S, int W, uint64_t seed, uint64_t row0, size_t count,
                               int bits, hipStream_t st);
 hipError_t launch_gather_rows(const uint32_t* T, size_t tstride, uint32_t tcount, int S, uint64_t seed, uint64_t row0,

@@ -63,7 +63,7 @@ EXPORTS = [
     "dds_opecol_search_mask", "dds_ctx_cache_stats",
     "dds_strtab_append", "dds_strtab_write_rows", "dds_strtab_set_live", "dds_strtab_rows", "dds_strtab_live_count",
     "dds_strtab_stats", "dds_strtab_truncate", "dds_host_register", "dds_host_unregister", "dds_host_alloc",
-    "dds_host_free",
+    "dds_host_free", "dds_paillier_decrypt_batch_crt", "dds_col_decrypt_paillier",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -136,6 +136,10 @@ _sig("dds_col_fill_table_synth", C.c_int, C.c_void_p, C.c_char_p, _sz, _sz, C.c_
 _sig("dds_col_fill_random", C.c_int, C.c_void_p, _sz, C.c_uint64, C.c_uint64, _sz)
 _sig("dds_col_encrypt_paillier", C.c_int, C.c_void_p, C.c_void_p, _sz, C.c_void_p, _sz, C.c_char_p, _sz, C.c_char_p,
      _sz, C.c_char_p, _sz, C.c_char_p, _sz)
+_sig("dds_paillier_decrypt_batch_crt", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz,
+     C.c_char_p, _sz, _sz, _u8p, _sz)
+_sig("dds_col_decrypt_paillier", C.c_int, C.c_void_p, _sz, _sz, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz,
+     _u8p, _sz)
 _sig("dds_modexp_batch", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz, _sz, _u8p)
 for _n in ("dds_sum_all_dec", "dds_mult_all_dec"):
     _sig(_n, C.c_int, C.c_void_p, C.POINTER(C.c_char_p), _sz, C.c_char_p, C.c_char_p, _sz, _szp)
@@ -482,6 +486,17 @@ class Engine:
         raw = bytes(out)
         return [int.from_bytes(raw[i * nb:(i + 1) * nb], "big") for i in range(len(rs))]
 
+    def paillier_decrypt_batch_crt(self, p: int, q: int, g: int, cs) -> list[int]:
+        """HomoAdd.decrypt(c, PaillierKey) for each c in cs (values in [0, n^2), coprime to n)."""
+        cs = [int(c) for c in cs]
+        nb, cw = nbytes(p * q), max([1] + [nbytes(c) for c in cs])
+        out = (C.c_uint8 * (nb * max(1, len(cs))))()
+        _check(_lib.dds_paillier_decrypt_batch_crt(self._h, int_to_be(p, nbytes(p)), nbytes(p), int_to_be(q, nbytes(q)),
+                                                   nbytes(q), int_to_be(g, nbytes(g)), nbytes(g), ints_to_be(cs, cw),
+                                                   cw, len(cs), out, nb), "dds_paillier_decrypt_batch_crt")
+        raw = bytes(out)
+        return [int.from_bytes(raw[i * nb:(i + 1) * nb], "big") for i in range(len(cs))]
+
     def modexp_batch(self, modulus: int, exponent: int, bases) -> list[int]:
         """out[i] = bases[i]^exponent mod modulus (HomoMult.encrypt for an RSA key)."""
         bases = [int(x) for x in bases]
@@ -681,6 +696,20 @@ class Column(_Mutable):
                                              int_to_be(n, nbytes(n)), nbytes(n), int_to_be(g, nbytes(g)), nbytes(g),
                                              pb, nbytes(p) if p else 0, qb, nbytes(q) if q else 0),
                "dds_col_encrypt_paillier")
+
+    def decrypt_paillier_buffer(self, first: int, count: int, p: int, q: int, g: int,
+                                n_bytes: int | None = None) -> np.ndarray:
+        """HomoAdd.decrypt of rows [first, first+count) of a column over (p*q)^2 (dds_col_decrypt_paillier):
+        big-endian plaintexts, uint8 [count, n_bytes] (n_bytes defaults to the byte length of n)."""
+        nb = nbytes(p * q) if n_bytes is None else n_bytes
+        out = np.empty((max(1, count), max(1, nb)), dtype=np.uint8)
+        _check(_lib.dds_col_decrypt_paillier(self._h, first, count, int_to_be(p, nbytes(p)), nbytes(p),
+                                             int_to_be(q, nbytes(q)), nbytes(q), int_to_be(g, nbytes(g)), nbytes(g),
+                                             out.ctypes.data_as(_u8p), nb), "dds_col_decrypt_paillier")
+        return out[:count]
+
+    def decrypt_paillier(self, first: int, count: int, p: int, q: int, g: int) -> list[int]:
+        return [int.from_bytes(r.tobytes(), "big") for r in self.decrypt_paillier_buffer(first, count, p, q, g)]
 
 
 OPE_CLS_LACKS, OPE_CLS_LAST, OPE_CLS_INNER = 0, 1, 2

@@ -405,6 +405,22 @@ int dds_paillier_encrypt_batch_crt(dds_ctx* ctx, const uint8_t* p_be, size_t p_b
                                    size_t q_bytes, const uint8_t* g_be, size_t g_bytes, const uint32_t* m,
                                    const uint8_t* r_be, size_t r_width, size_t count, uint8_t* out, size_t nsq_bytes);
 
+/* HomoAdd.decrypt(c, PaillierKey) (SJHomoLibProvider.scala:68) for `count` ciphertexts (big-endian,
+ * `width` bytes each, values in [0, n^2): DDS_E_RANGE otherwise, and for a c not coprime to n).
+ * out: count plaintexts m < n, n_bytes each, big-endian. p, q in either order. Computed mod p^2 and
+ * q^2 (exponents p-1, q-1), L function and recombination on the device; equals L(c^lambda mod n^2) mu mod n.
+ * n_bytes below the byte length of n: DDS_E_BUFSIZE; p, q not distinct odd primes, a g whose
+ * L(g^(d-1) mod d^2) is not invertible, or factors too unbalanced for the half-width limbs: DDS_E_ARG.
+ * After an error the contents of out are unspecified. With dds_ctx_set_timing on, a decrypt call adds
+ * the device time of its kernels to total_ms and that of its exponentiation ladders to fold_ms. */
+int dds_paillier_decrypt_batch_crt(dds_ctx*, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be, size_t q_bytes,
+                                   const uint8_t* g_be, size_t g_bytes, const uint8_t* c_be, size_t width,
+                                   size_t count, uint8_t* out, size_t n_bytes);
+/* The same for rows [first, first+count) of a resident column over n^2 (positional, like dds_col_read). */
+int dds_col_decrypt_paillier(dds_col* col, size_t first, size_t count, const uint8_t* p_be, size_t p_bytes,
+                             const uint8_t* q_be, size_t q_bytes, const uint8_t* g_be, size_t g_bytes,
+                             uint8_t* out, size_t n_bytes);
+
 /* Batched modular exponentiation out[i] = base[i]^exp mod modulus (mod_bytes each):
  * HomoMult.encrypt(pk, m) = m^e mod n (SJHomoLibProvider.scala:59) and decrypt-side
  * checks. Bases are validated like fold operands. */
