@@ -181,6 +181,25 @@ inline Limbs pow2(size_t e) {
   return r;
 }
 
+// x mod 2^t
+inline Limbs low_bits(const Limbs& x, size_t t) {
+  Limbs r(x.begin(), x.begin() + std::min(x.size(), (t + 31) / 32));
+  if (t % 32 && r.size() == (t + 31) / 32) r.back() &= (1u << (t % 32)) - 1u;
+  trim(r);
+  return r;
+}
+
+// N^-1 mod 2^k for an odd N, k >= 1 (Newton: inv <- inv (2 - N inv) doubles the correct low bits)
+inline Limbs inv_mod_pow2(const Limbs& N, size_t k) {
+  Limbs inv{1};
+  const Limbs two_k2 = add(pow2(k), Limbs{2});
+  for (size_t ok = 1; ok < k; ok *= 2) {
+    const Limbs t = low_bits(mul(N, inv), k);
+    inv = low_bits(mul(inv, low_bits(sub(two_k2, t), k)), k);
+  }
+  return inv;
+}
+
 inline Limbs powmod(Limbs base, const Limbs& e, const Limbs& m) {
   Limbs r = mod(Limbs{1}, m);
   base = mod(base, m);

@@ -129,14 +129,7 @@ int get_mod(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, std::shared_p
     const size_t k3 = (size_t)mc->W3 * mc->S3;
     // a tree product of raw rows a, b < 2^(W S) stays < 2N when a b / R3 < N (forced-wide shapes fail this)
     mc->tree_direct = k3 + bn::bit_length(N) - 1 >= 2 * (size_t)mc->W * S;
-    bn::Limbs inv{1};  // N^-1 mod 2^k3 by Newton: inv <- inv (2 - N inv), doubling the correct bits
-    const bn::Limbs two{2};
-    for (size_t ok = 1; ok < k3; ok *= 2) {
-      const bn::Limbs t = low_bits(bn::mul(N, inv), k3);
-      inv = low_bits(bn::mul(inv, low_bits(bn::sub(bn::add(bn::pow2(k3), two), t), k3)), k3);
-    }
-    bn::trim(inv);
-    const bn::Limbs np = bn::sub(bn::pow2(k3), inv);  // -N^-1 mod R3 (inv != 0: N odd)
+    const bn::Limbs np = bn::sub(bn::pow2(k3), bn::inv_mod_pow2(N, k3));  // -N^-1 mod R3 (N odd: != 0)
     std::vector<uint32_t> h3;
     const bn::Limbs r3 = bn::mod(bn::pow2(k3), N);
     for (const bn::Limbs& v : {N, np, N, bn::add(N, N), bn::add(bn::add(N, N), N), bn::mod(bn::mul(r3, r3), N)}) {
@@ -529,6 +522,37 @@ int emit_be(const bn::Limbs& v, size_t width, uint8_t* out, size_t out_cap, size
   return DDS_OK;
 }
 
+int rows_to_be(Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride, size_t count,
+               bool reduce, uint8_t* out, size_t width, hipEvent_t before_copy) {
+  if (count == 0) return DDS_OK;
+  const int S = mc.S;
+  if (S <= kEgressMaxLimbs) {  // big-endian bytes on the GPU (k_egress_be), one copy out per piece
+    const uint32_t* nmod = reduce ? mc.d + (size_t)kConstN * S : nullptr;
+    const size_t piece = std::max<size_t>(1, ((size_t)256 << 20) / width);  // bounded device staging
+    for (size_t b = 0; b < count; b += piece) {
+      const size_t n = std::min(piece, count - b);
+      HIP_TRY(w->misc.ensure(n * width));
+      HIP_TRY(launch_egress_be(X + b, stride, n, S, mc.W, nmod, width, w->misc.as<uint8_t>(), st));
+      if (before_copy && b == 0) HIP_TRY(hipEventRecord(before_copy, st));
+      HIP_TRY(hipMemcpyAsync(out + b * width, w->misc.p, n * width, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    return DDS_OK;
+  }
+  // shapes wider than the egress kernel's: the rows' limbs (not the stride padding) to the host, codec here
+  std::vector<uint32_t> h((size_t)S * count), limbs(S);
+  if (before_copy) HIP_TRY(hipEventRecord(before_copy, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy2D(h.data(), count * 4, X, stride * 4, count * 4, (size_t)S, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < count; ++i) {
+    for (int l = 0; l < S; ++l) limbs[l] = h[(size_t)l * count + i];
+    bn::Limbs v = mc.value(limbs.data());
+    if (reduce) v = bn::mod(v, mc.N);
+    if (!bn::to_be(v, out + i * width, width)) return fail(DDS_E_RANGE, "result does not fit");
+  }
+  return DDS_OK;
+}
+
 
 
 int ingest(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint8_t* ops, size_t width, size_t count,
@@ -900,14 +924,6 @@ int product_tree(dds_ctx* ctx, const std::vector<uint32_t>& h, size_t count, siz
   return DDS_OK;
 }
 
-// x mod 2^t
-bn::Limbs low_bits(const bn::Limbs& x, size_t t) {
-  bn::Limbs r(x.begin(), x.begin() + std::min(x.size(), (t + 31) / 32));
-  if (t % 32 && r.size() == (t + 31) / 32) r.back() &= (1u << (t % 32)) - 1u;
-  bn::trim(r);
-  return r;
-}
-
 // Product of magnitudes xs[i] (signs negs[i]) mod an EVEN modulus M (or M == 1), count >= 2. A
 // Montgomery fold needs an odd modulus, so M = 2^t * Q (Q odd) is split: prod mod Q by the
 // Montgomery fold (in the shape of M's width, so operands as wide as M's capacity fit), prod mod 2^t
@@ -948,7 +964,7 @@ int fold_even_modulus(dds_ctx* ctx, const bn::Limbs& M, const std::vector<bn::Li
     const size_t cap16 = (t + 15) / 16;
     std::vector<uint32_t> h(count * cap16, 0);
     for (size_t i = 0; i < count; ++i) {
-      const bn::Limbs lo = low_bits(ys[i], t);
+      const bn::Limbs lo = bn::low_bits(ys[i], t);
       for (size_t k = 0; k < lo.size() && 2 * k < cap16; ++k) {
         h[i * cap16 + 2 * k] = lo[k] & 0xFFFFu;
         if (2 * k + 1 < cap16) h[i * cap16 + 2 * k + 1] = lo[k] >> 16;
@@ -956,20 +972,16 @@ int fold_even_modulus(dds_ctx* ctx, const bn::Limbs& M, const std::vector<bn::Li
     }
     int rc = product_tree(ctx, h, count, cap16, cap16, &r2);
     if (rc) return rc;
-    r2 = low_bits(r2, t);
+    r2 = bn::low_bits(r2, t);
   }
   // CRT: r = rq + Q * ((r2 - rq) * Q^-1 mod 2^t)
   bn::Limbs r = rq;
   if (t > 0) {
     const bn::Limbs two_t = bn::pow2(t);
-    bn::Limbs qinv{1};  // Newton: qinv <- qinv (2 - Q qinv) mod 2^t, doubling the correct bits
-    for (size_t bits = 1; bits < t; bits *= 2) {
-      const bn::Limbs qq = low_bits(bn::mul(Q, qinv), t);
-      qinv = low_bits(bn::mul(qinv, bn::sub(bn::add(two_t, bn::Limbs{2}), qq)), t);
-    }
-    const bn::Limbs rqt = low_bits(rq, t);
+    const bn::Limbs qinv = bn::inv_mod_pow2(Q, t);
+    const bn::Limbs rqt = bn::low_bits(rq, t);
     const bn::Limbs d = bn::cmp(r2, rqt) >= 0 ? bn::sub(r2, rqt) : bn::sub(bn::add(r2, two_t), rqt);
-    r = bn::add(rq, bn::mul(Q, low_bits(bn::mul(d, qinv), t)));
+    r = bn::add(rq, bn::mul(Q, bn::low_bits(bn::mul(d, qinv), t)));
   }
   size_t nneg = 0;
   for (bool b : negs) nneg += b;
@@ -1512,24 +1524,7 @@ int dds_modmul_pairs(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, cons
     if ((rc = ingest(ctx, w, wl.st, *mc, b, width, n, w->in2, w->x2.as<uint32_t>(), stride))) return rc;
     HIP_TRY(launch_pairs(S, w->x.as<uint32_t>(), w->x2.as<uint32_t>(), stride, n, mc->d, mc->n0,
                          w->p0.as<uint32_t>(), wl.st));
-    if (S <= kEgressMaxLimbs) {  // canonical products -> big-endian bytes on the GPU, one copy out
-      HIP_TRY(w->misc.ensure(n * mod_bytes));
-      HIP_TRY(launch_egress_be(w->p0.as<uint32_t>(), stride, n, S, mc->W, nullptr, mod_bytes, w->misc.as<uint8_t>(),
-                               wl.st));
-      HIP_TRY(hipMemcpyAsync(out, w->misc.p, n * mod_bytes, hipMemcpyDeviceToHost, wl.st));
-      HIP_TRY(hipStreamSynchronize(wl.st));
-      return DDS_OK;
-    }
-    std::vector<uint32_t> h((size_t)S * stride);
-    HIP_TRY(hipMemcpyAsync(h.data(), w->p0.p, h.size() * 4, hipMemcpyDeviceToHost, wl.st));
-    HIP_TRY(hipStreamSynchronize(wl.st));
-    std::vector<uint32_t> limbs(S);
-    for (size_t i = 0; i < n; ++i) {
-      for (int l = 0; l < S; ++l) limbs[l] = h[(size_t)l * stride + i];
-      if (!bn::to_be(mc->value(limbs.data()), out + i * mod_bytes, mod_bytes))
-        return fail(DDS_E_RANGE, "result does not fit");
-    }
-    return DDS_OK;
+    return rows_to_be(w, wl.st, *mc, w->p0.as<uint32_t>(), stride, n, false, out, mod_bytes);  // k_pairs canonicalises
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");
   } catch (...) {
@@ -1779,37 +1774,12 @@ int dds_col_read(dds_col* col, size_t first, size_t count, uint8_t* out) {
     if (!col) return fail(DDS_E_ARG, "bad arguments");
     std::shared_lock<std::shared_mutex> lk(col->mu);
     if ((count && !out) || first + count > col->count) return fail(DDS_E_ARG, "bad arguments");
-    const int S = col->mc->S;
-    if (count && S <= kEgressMaxLimbs) {  // rows (< 2N) -> canonical big-endian bytes on the GPU
-      WorkerLease wl(col->ctx);
-      int rc;
-      if ((rc = wl.acquire())) return rc;
-      Worker* w = wl.w;
-      const size_t bytes = col->mc->bytes;
-      for (size_t b = 0; b < count;) {  // bounded device staging: chunks of <= 256 MiB of bytes
-        const size_t n = std::min(count - b, std::max<size_t>(1, ((size_t)256 << 20) / bytes));
-        HIP_TRY(w->misc.ensure(n * bytes));
-        HIP_TRY(launch_egress_be(col->d + first + b, col->stride, n, S, col->mc->W, col->mc->d + (size_t)kConstN * S,
-                                 bytes, w->misc.as<uint8_t>(), wl.st));
-        HIP_TRY(hipMemcpyAsync(out + b * bytes, w->misc.p, n * bytes, hipMemcpyDeviceToHost, wl.st));
-        HIP_TRY(hipStreamSynchronize(wl.st));
-        b += n;
-      }
-      return DDS_OK;
-    }
-    std::vector<uint32_t> h((size_t)S * count);
-    if (count)
-      HIP_TRY(hipMemcpy2D(h.data(), count * 4, col->d + first, col->stride * 4, count * 4, (size_t)S,
-                          hipMemcpyDeviceToHost));
-    std::vector<uint32_t> limbs(S);
-    for (size_t i = 0; i < count; ++i) {
-      for (int l = 0; l < S; ++l) limbs[l] = h[(size_t)l * count + i];
-      bn::Limbs v = col->mc->value(limbs.data());
-      if (bn::cmp(v, col->mc->N) >= 0) v = bn::mod(v, col->mc->N);  // rows are kept < 2N
-      if (!bn::to_be(v, out + i * col->mc->bytes, col->mc->bytes))
-        return fail(DDS_E_RANGE, "row does not fit");
-    }
-    return DDS_OK;
+    if (count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    int rc;
+    if ((rc = wl.acquire())) return rc;
+    // rows are kept < 2N: canonical residues out
+    return rows_to_be(wl.w, wl.st, *col->mc, col->d + first, col->stride, count, true, out, col->mc->bytes);
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");
   }
@@ -1956,610 +1926,6 @@ int dds_col_fold_partial_device(dds_col* col, size_t first, size_t count, uint32
   }
 }
 
-// ---- modular exponentiation / Paillier encryption --------------------------------
-namespace {
-// Sliding-window schedule of a uniform exponent E (left to right): sched[0] = index of the
-// leading window's odd power, then (nsq << 16) | (idx + 1) per later window (idx + 1 == 0:
-// trailing squarings only). Returns the number of odd powers the table must hold.
-int window_schedule(const bn::Limbs& E, std::vector<uint32_t>* sched) {
-  sched->clear();
-  const int nb = (int)bn::bit_length(E);
-  if (nb == 0) return 1;
-  auto bit = [&](int i) { return (E[(size_t)i >> 5] >> (i & 31)) & 1u; };
-  // window width minimising table + multiplies (table of 2^(w-1) odd powers per row)
-  const int w = nb <= 24 ? 1 : nb <= 80 ? 3 : nb <= 240 ? 4 : 5;
-  int i = nb - 1;
-  uint32_t pending_sq = 0;
-  bool first = true;
-  while (i >= 0) {
-    if (!bit(i)) {
-      ++pending_sq;
-      --i;
-      continue;
-    }
-    int j = std::max(i - w + 1, 0);
-    while (!bit(j)) ++j;  // window [i..j] ends on a set bit
-    uint32_t v = 0;
-    for (int k = i; k >= j; --k) v = (v << 1) | bit(k);
-    const uint32_t idx = (v - 1) / 2;
-    if (first) {
-      sched->push_back(idx);
-      first = false;
-    } else {
-      pending_sq += (uint32_t)(i - j + 1);
-      sched->push_back((pending_sq << 16) | (idx + 1));
-    }
-    pending_sq = 0;
-    i = j - 1;
-  }
-  while (pending_sq > 0) {  // trailing zero bits: squarings only, <= 0xFFFF per entry
-    const uint32_t c = std::min<uint32_t>(pending_sq, 0xFFFF);
-    sched->push_back(c << 16);
-    pending_sq -= c;
-  }
-  return 1 << (w - 1);
-}
-
-// out[i] = g^m[i] * x[i]^E mod N on the device (d_m == nullptr: x[i]^E). x rows are rW,
-// fully normalised, < 2N. Processes the batch in equal chunks so the per-row window table
-// (nodd * S words per row) stays within kModexpTabBytes of HBM.
-constexpr size_t kModexpTabBytes = (size_t)8 << 30;
-int modexp_device(Worker* w, hipStream_t st, ModConsts& mc, const bn::Limbs& E, const bn::Limbs* g,
-                  const uint32_t* d_x, size_t xstride, const uint32_t* d_m, size_t count, uint32_t* d_out,
-                  size_t ostride) {
-  if (count == 0) return DDS_OK;
-  const int S = mc.S;
-  std::vector<uint32_t> sched;
-  const int nodd = window_schedule(E, &sched);
-  std::vector<uint32_t> gr;
-  if (d_m) gr = mc.rw(bn::mod(bn::mul(bn::mod(*g, mc.N), mc.Rmod), mc.N));
-  else gr.assign((size_t)S, 0);
-  const size_t sched_words = std::max<size_t>(sched.size(), 1);
-  HIP_TRY(w->y.ensure((gr.size() + sched_words) * 4));
-  uint32_t* d_gr = w->y.as<uint32_t>();
-  uint32_t* d_sched = d_gr + gr.size();
-  HIP_TRY(hipMemcpyAsync(d_gr, gr.data(), gr.size() * 4, hipMemcpyHostToDevice, st));
-  if (!sched.empty())
-    HIP_TRY(hipMemcpyAsync(d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice, st));
-  const size_t row_bytes = (size_t)nodd * S * 4;
-  // equal chunks (a short last chunk would leave most CUs idle for a whole ladder)
-  const size_t cap = std::max<size_t>(64, kModexpTabBytes / row_bytes / 64 * 64);
-  const size_t nch = (count + cap - 1) / cap;
-  const size_t chunk = round_up((count + nch - 1) / nch, 64);
-  HIP_TRY(w->tab.ensure((size_t)nodd * S * chunk * 4));
-  for (size_t c0 = 0; c0 < count; c0 += chunk) {
-    const size_t cc = std::min(chunk, count - c0);
-    HIP_TRY(launch_modexp_pre(S, d_x + c0, xstride, cc, mc.d, mc.dqm, mc.n0, nodd, w->tab.as<uint32_t>(), chunk, st));
-    HIP_TRY(launch_modexp_ladder(S, w->tab.as<uint32_t>(), chunk, d_m ? d_m + c0 : nullptr, cc, mc.d, mc.dqm, d_gr, d_sched,
-                                 (int)sched.size(), mc.n0, d_out + c0, ostride, st));
-  }
-  HIP_TRY(hipStreamSynchronize(st));  // host vectors above must outlive the async copies
-  return DDS_OK;
-}
-
-int encrypt_device(Worker* w, hipStream_t st, ModConsts& mc, const bn::Limbs& n, const bn::Limbs& g,
-                   const uint32_t* d_m, const uint32_t* d_rcol, size_t rstride, size_t count, uint32_t* d_out,
-                   size_t ostride, bool use_n_exponent) {
-  return modexp_device(w, st, mc, use_n_exponent ? n : bn::Limbs{}, &g, d_rcol, rstride, d_m, count, d_out, ostride);
-}
-}  // namespace
-
-// CRT form of a Paillier key (p, q): per-modulus constants of p^2, q^2, n^2 and the Garner
-// constants c1R = (q^2)^-1 R_p, c2R = -(q^2)^-1 R_p (mod p^2), q2R = q^2 R_n (mod n^2).
-// Decryption constants of one (p, q, g) (decrypt_crt_device), built on the first decrypt with that g, so
-// encrypt-only users pay nothing. For factor i of (p, q), at d + off[i], in the limbs of its square's shape:
-//   2^(j W_n)·R_d | R_d (mod d^2): x_d = c mod d^2 from the halves of c split at limb j of the n^2 layout
-//   h_d·R_d | d^2 - h_d, with h_d = L_d(g^(d-1) mod d^2)^-1 mod d
-//   d^-1 mod 2^(sdiv W_d), sdiv = ceil((bits(d) + 1) / W_d) limbs (the exact division by d)
-// (S_d limbs each, d the factor); then, at d + off_e, e_p·R_n | e_q·R_n (mod n) in the limbs of n's shape.
-struct DecKey {
-  std::shared_ptr<ModConsts> mnn;  // modulus n: the recombination and the plaintexts' layout
-  bn::Limbs e[2];                  // p - 1, q - 1
-  int j = 0, sdiv[2] = {0, 0};
-  size_t off[2] = {0, 0}, off_e = 0;
-  uint32_t* d = nullptr;
-  ~DecKey() {
-    if (d) (void)hipFree(d);
-  }
-};
-
-struct CrtKey {
-  std::shared_ptr<ModConsts> mp, mq, mn;
-  bn::Limbs n, p, q;
-  uint32_t* d = nullptr;  // c1R | c2R (2 Sp limbs) | q2R (Sn limbs)
-  std::mutex dmu;
-  std::map<bn::Limbs, std::shared_ptr<DecKey>> dec;  // by g: two keys over the same p, q do not share h_d
-  ~CrtKey() {
-    if (d) (void)hipFree(d);
-  }
-};
-
-namespace {
-int get_crt_key(dds_ctx* ctx, const bn::Limbs& p, const bn::Limbs& q, std::shared_ptr<CrtKey>* out) {
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    auto it = ctx->crt_keys.find({p, q});
-    if (it != ctx->crt_keys.end()) {
-      *out = it->second;
-      return DDS_OK;
-    }
-  }
-  if (p.empty() || q.empty() || !(p[0] & 1u) || !(q[0] & 1u) || bn::cmp(p, q) == 0 || bn::bit_length(p) < 2 ||
-      bn::bit_length(q) < 2)
-    return fail(DDS_E_ARG, "p, q must be distinct odd primes");
-  auto k = std::make_shared<CrtKey>();
-  k->n = bn::mul(p, q);
-  k->p = p;
-  k->q = q;
-  const bn::Limbs p2 = bn::mul(p, p), q2 = bn::mul(q, q), n2 = bn::mul(k->n, k->n);
-  auto be = [](const bn::Limbs& v) {
-    std::vector<uint8_t> b(bn::byte_length(v));
-    bn::to_be(v, b.data(), b.size());
-    return b;
-  };
-  int rc;
-  auto bp = be(p2), bq = be(q2), bn2 = be(n2);
-  if ((rc = get_mod(ctx, bp.data(), bp.size(), &k->mp)) || (rc = get_mod(ctx, bq.data(), bq.size(), &k->mq)) ||
-      (rc = get_mod(ctx, bn2.data(), bn2.size(), &k->mn)))
-    return rc;
-  // (q^2)^-1 mod p^2 = (q^2)^(p(p-1)-1) (Euler, p prime); verified below
-  const bn::Limbs phi = bn::mul(p, bn::sub(p, bn::Limbs{1}));
-  const bn::Limbs qinv = bn::powmod(bn::mod(q2, p2), bn::sub(phi, bn::Limbs{1}), p2);
-  if (bn::cmp(bn::mod(bn::mul(qinv, q2), p2), bn::Limbs{1}) != 0) return fail(DDS_E_ARG, "p, q must be distinct primes");
-  const ModConsts &mp = *k->mp, &mn = *k->mn;
-  std::vector<uint32_t> host;
-  auto put = [&](const std::vector<uint32_t>& v) { host.insert(host.end(), v.begin(), v.end()); };
-  put(mp.rw(bn::mulmod(qinv, mp.Rmod, p2)));
-  put(mp.rw(bn::mulmod(bn::sub(p2, qinv), mp.Rmod, p2)));
-  put(mn.rw(bn::mulmod(q2, mn.Rmod, n2)));
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&k->d, host.size() * 4) != hipSuccess)
-    return fail(DDS_E_NOMEM, "crt const alloc");
-  HIP_TRY(hipMemcpy(k->d, host.data(), host.size() * 4, hipMemcpyHostToDevice));
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  auto it = ctx->crt_keys.find({p, q});
-  if (it != ctx->crt_keys.end()) {
-    *out = it->second;
-    return DDS_OK;
-  }
-  if (ctx->crt_keys.size() > 16) ctx->crt_keys.clear();
-  ctx->crt_keys.emplace(std::make_pair(p, q), k);
-  *out = k;
-  return DDS_OK;
-}
-
-// The CRT halves need r < R_p, R_q (r fits the half-width limb layout) and y_q < R_p.
-bool crt_fits(const CrtKey& k) {
-  const size_t cap_p = (size_t)k.mp->S * k.mp->W - 2, cap_q = (size_t)k.mq->S * k.mq->W - 2;
-  const size_t nb = bn::bit_length(k.n);
-  return nb <= cap_p && nb <= cap_q && k.mq->bits <= cap_p;
-}
-
-// out = g^m r^n mod n^2 for rows of r (n^2 layout, values < 2^bits(n)) through the CRT halves
-int encrypt_crt_device(Worker* w, hipStream_t st, CrtKey& k, const bn::Limbs& g, const uint32_t* d_m,
-                       const uint32_t* d_r, size_t rstride, size_t count, uint32_t* d_out, size_t ostride) {
-  ModConsts &mp = *k.mp, &mq = *k.mq, &mn = *k.mn;
-  const size_t chunk = std::min<size_t>(round_up(count, 64), (size_t)1 << 20);
-  const size_t sp = (size_t)mp.S * chunk * 4, sq = (size_t)mq.S * chunk * 4, sn = (size_t)mn.S * chunk * 4;
-  const size_t sizes[7] = {sp, sq, sp, sq, sp, sn, sn};
-  for (int i = 0; i < 7; ++i) HIP_TRY(w->crt[i].ensure(sizes[i]));
-  HIP_TRY(w->flags.ensure(16));
-  HIP_TRY(hipMemsetAsync(w->flags.as<uint32_t>() + 1, 0, 4, st));
-  uint32_t* fl = w->flags.as<uint32_t>() + 1;
-  uint32_t *A = w->crt[0].as<uint32_t>(), *B = w->crt[1].as<uint32_t>(), *C = w->crt[2].as<uint32_t>(),
-           *D = w->crt[3].as<uint32_t>(), *E = w->crt[4].as<uint32_t>(), *F = w->crt[5].as<uint32_t>(),
-           *Gq = w->crt[6].as<uint32_t>();
-  int rc;
-  for (size_t c0 = 0; c0 < count; c0 += chunk) {
-    const size_t cc = std::min(chunk, count - c0);
-    HIP_TRY(launch_repack(d_r + c0, rstride, mn.S, mn.W, A, chunk, mp.S, mp.W, cc, fl, st));
-    HIP_TRY(launch_repack(d_r + c0, rstride, mn.S, mn.W, B, chunk, mq.S, mq.W, cc, fl, st));
-    if ((rc = modexp_device(w, st, mp, k.n, &g, A, chunk, d_m + c0, cc, C, chunk))) return rc;
-    if ((rc = modexp_device(w, st, mq, k.n, &g, B, chunk, d_m + c0, cc, D, chunk))) return rc;
-    HIP_TRY(launch_repack(D, chunk, mq.S, mq.W, E, chunk, mp.S, mp.W, cc, fl, st));
-    HIP_TRY(launch_crt_h(mp.S, C, E, chunk, cc, mp.d, k.d, mp.n0, A, st));
-    HIP_TRY(launch_repack(A, chunk, mp.S, mp.W, F, chunk, mn.S, mn.W, cc, fl, st));
-    HIP_TRY(launch_repack(D, chunk, mq.S, mq.W, Gq, chunk, mn.S, mn.W, cc, fl, st));
-    HIP_TRY(launch_crt_out(mn.S, F, Gq, chunk, cc, mn.d, k.d + 2 * (size_t)mp.S, mn.n0, d_out + c0, ostride, st));
-  }
-  uint32_t flags = 0;
-  HIP_TRY(read_sync(w, st, fl, &flags, 4));
-  if (flags) return fail(DDS_E_RANGE, "r does not fit below 2^bits(n)");
-  return DDS_OK;
-}
-
-// N^-1 mod 2^k for an odd N (Newton: inv <- inv (2 - N inv) doubles the correct low bits)
-void inv_mod_pow2(const bn::Limbs& N, size_t k, bn::Limbs* out) {
-  bn::Limbs& inv = *out;
-  inv = bn::Limbs{1};
-  const bn::Limbs two{2};
-  for (size_t ok = 1; ok < k; ok *= 2) {
-    const bn::Limbs t = low_bits(bn::mul(N, inv), k);
-    inv = low_bits(bn::mul(inv, low_bits(bn::sub(bn::add(bn::pow2(k), two), t), k)), k);
-  }
-  bn::trim(inv);
-}
-
-int get_dec_key(dds_ctx* ctx, CrtKey& k, const bn::Limbs& g, std::shared_ptr<DecKey>* out) {
-  {
-    std::lock_guard<std::mutex> lk(k.dmu);
-    auto it = k.dec.find(g);
-    if (it != k.dec.end()) {
-      *out = it->second;
-      return DDS_OK;
-    }
-  }
-  auto dk = std::make_shared<DecKey>();
-  const ModConsts& mn = *k.mn;
-  // Shape check (as crt_fits for encrypt): c, a row of the n^2 layout below 2 n^2, splits at limb j into
-  // c_lo (j W_n bits) and c_hi; both must fit the limbs of p^2 and of q^2 with the usual 2 bits to spare
-  const size_t cbits = mn.bits + 1;
-  dk->j = (int)((cbits + 2 * (size_t)mn.W - 1) / (2 * (size_t)mn.W));
-  const size_t lo = (size_t)dk->j * mn.W, hi = cbits > lo ? cbits - lo : 0;
-  for (const ModConsts* md : {k.mp.get(), k.mq.get()}) {
-    const size_t cap = (size_t)md->S * md->W - 2;
-    if (dk->j < 1 || dk->j >= mn.S || lo > cap || hi > cap)
-      return fail(DDS_E_ARG, "factors too unbalanced for CRT decrypt");
-  }
-  int rc;
-  {
-    std::vector<uint8_t> nb(bn::byte_length(k.n));
-    bn::to_be(k.n, nb.data(), nb.size());
-    if ((rc = get_mod(ctx, nb.data(), nb.size(), &dk->mnn))) return rc;
-  }
-  const ModConsts& mnn = *dk->mnn;
-  const bn::Limbs one{1}, two{2};
-  std::vector<uint32_t> host;
-  auto put = [&](const std::vector<uint32_t>& v) { host.insert(host.end(), v.begin(), v.end()); };
-  const bn::Limbs* ds[2] = {&k.p, &k.q};
-  const ModConsts* mds[2] = {k.mp.get(), k.mq.get()};
-  for (int i = 0; i < 2; ++i) {
-    const bn::Limbs& d = *ds[i];
-    const ModConsts& md = *mds[i];
-    const bn::Limbs& d2 = md.N;
-    dk->e[i] = bn::sub(d, one);
-    dk->off[i] = host.size();
-    put(md.rw(bn::mulmod(bn::mod(bn::pow2(lo), d2), md.Rmod, d2)));
-    put(md.rw(md.Rmod));
-    // h_d = L_d(g^(d-1) mod d^2)^-1 mod d, by Euler (d prime; verified below)
-    const bn::Limbs v = bn::powmod(bn::mod(g, d2), dk->e[i], d2);
-    if (v.empty()) return fail(DDS_E_ARG, "g is not coprime to n");
-    bn::Limbs l;
-    if (!bn::mod(bn::sub(v, one), d, &l).empty()) return fail(DDS_E_ARG, "p, q must be distinct primes");
-    l = bn::mod(l, d);
-    const bn::Limbs h = bn::powmod(l, bn::sub(d, two), d);
-    if (bn::cmp(bn::mulmod(h, l, d), one) != 0) return fail(DDS_E_ARG, "L(g^(d-1) mod d^2) is not invertible mod d");
-    put(md.rw(bn::mulmod(h, md.Rmod, d2)));
-    put(md.rw(bn::sub(d2, h)));
-    dk->sdiv[i] = (int)((bn::bit_length(d) + 1 + md.W - 1) / md.W);
-    if (dk->sdiv[i] > md.S) return fail(DDS_E_UNSUPPORTED, "factor too wide for its shape");
-    bn::Limbs dinv;
-    inv_mod_pow2(d, (size_t)dk->sdiv[i] * md.W, &dinv);
-    put(bn::to_rw(dinv, md.S, md.W));
-  }
-  dk->off_e = host.size();
-  for (int i = 0; i < 2; ++i) {  // e_p = q (q^-1 mod p), e_q = p (p^-1 mod q)
-    const bn::Limbs &d = *ds[i], &o = *ds[1 - i];
-    const bn::Limbs oi = bn::powmod(bn::mod(o, d), bn::sub(d, two), d);
-    if (bn::cmp(bn::mulmod(oi, o, d), one) != 0) return fail(DDS_E_ARG, "p, q must be distinct primes");
-    put(mnn.rw(bn::mulmod(bn::mul(o, oi), mnn.Rmod, k.n)));
-  }
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&dk->d, host.size() * 4) != hipSuccess)
-    return fail(DDS_E_NOMEM, "decrypt const alloc");
-  HIP_TRY(hipMemcpy(dk->d, host.data(), host.size() * 4, hipMemcpyHostToDevice));
-  std::lock_guard<std::mutex> lk(k.dmu);
-  auto it = k.dec.find(g);
-  if (it != k.dec.end()) {
-    *out = it->second;
-    return DDS_OK;
-  }
-  if (k.dec.size() > 8) k.dec.clear();
-  k.dec.emplace(g, dk);
-  *out = dk;
-  return DDS_OK;
-}
-
-// out[i] = HomoAdd.decrypt(c_i) for rows of c (n^2 layout, values < 2 n^2), big-endian, n_bytes each, through
-// the CRT halves (formulas at k_lfun_w). Chunks of at most 2^18 rows: 2048 workgroups of 128 rows still fill
-// the chip, at a quarter of the encrypt path's scratch. A row not coprime to n fails the call (DDS_E_RANGE).
-// With timing on (dds_ctx_set_timing) the kernels' device time goes to total_ms and the ladders' to fold_ms.
-int decrypt_crt_device(dds_ctx* ctx, Worker* w, hipStream_t st, CrtKey& k, DecKey& dk, const uint32_t* d_c,
-                       size_t cstride, size_t count, uint8_t* out, size_t n_bytes) {
-  ModConsts &mn = *k.mn, &mnn = *dk.mnn;
-  ModConsts* mds[2] = {k.mp.get(), k.mq.get()};
-  const size_t chunk = std::min<size_t>(round_up(count, 64), (size_t)1 << 18);
-  const size_t sh = (size_t)std::max(mds[0]->S, mds[1]->S) * chunk * 4, sn = (size_t)mnn.S * chunk * 4;
-  const size_t sizes[6] = {sh, sh, sh, sn, sn, sn};
-  for (int i = 0; i < 6; ++i) HIP_TRY(w->crt[i].ensure(sizes[i]));
-  HIP_TRY(w->flags.ensure(16));
-  uint32_t* fl = w->flags.as<uint32_t>() + 1;
-  HIP_TRY(hipMemsetAsync(fl, 0, 4, st));
-  uint32_t *A = w->crt[0].as<uint32_t>(), *B = w->crt[1].as<uint32_t>(), *C = w->crt[2].as<uint32_t>(),
-           *H = w->crt[5].as<uint32_t>();
-  const bool timed = ctx->timing.load();
-  float ladder_ms = 0, kernel_ms = 0;
-  uint64_t ladders = 0;
-  const bool dev_egress = mnn.S <= kEgressMaxLimbs;
-  std::vector<uint32_t> hh, limbs;
-  int rc;
-  for (size_t c0 = 0; c0 < count; c0 += chunk) {
-    const size_t cc = std::min(chunk, count - c0);
-    if (timed) HIP_TRY(hipEventRecord(w->ev[2], st));
-    for (int i = 0; i < 2; ++i) {
-      ModConsts& md = *mds[i];
-      const int S = md.S;
-      const uint32_t* kc = dk.d + dk.off[i];
-      uint32_t* Mn = w->crt[3 + i].as<uint32_t>();
-      HIP_TRY(launch_repack(d_c + (size_t)dk.j * cstride + c0, cstride, mn.S - dk.j, mn.W, A, chunk, S, md.W, cc, fl, st));
-      HIP_TRY(launch_repack(d_c + c0, cstride, dk.j, mn.W, B, chunk, S, md.W, cc, fl, st));
-      HIP_TRY(launch_crt_h(S, A, B, chunk, cc, md.d, kc, md.n0, C, st));  // x_d = c mod d^2
-      if (timed) HIP_TRY(hipEventRecord(w->ev[0], st));
-      if ((rc = modexp_device(w, st, md, dk.e[i], nullptr, C, chunk, nullptr, cc, A, chunk))) return rc;  // u_d
-      if (timed) {
-        float ms = 0;
-        HIP_TRY(hipEventRecord(w->ev[1], st));
-        HIP_TRY(hipEventSynchronize(w->ev[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
-        ladder_ms += ms;
-        ++ladders;
-      }
-      HIP_TRY(launch_lfun_w(S, A, chunk, cc, md.d, kc + 2 * (size_t)S, md.n0, B, st));
-      HIP_TRY(launch_lfun_div(B, A, chunk, S, dk.sdiv[i], md.W, kc + 4 * (size_t)S, C, cc, fl, st));
-      HIP_TRY(launch_repack(C, chunk, dk.sdiv[i], md.W, Mn, chunk, mnn.S, mnn.W, cc, fl, st));
-    }
-    HIP_TRY(launch_crt_h(mnn.S, w->crt[3].as<uint32_t>(), w->crt[4].as<uint32_t>(), chunk, cc, mnn.d, dk.d + dk.off_e,
-                         mnn.n0, H, st));
-    if (dev_egress) {
-      HIP_TRY(w->misc.ensure(cc * n_bytes));
-      HIP_TRY(launch_egress_be(H, chunk, cc, mnn.S, mnn.W, nullptr, n_bytes, w->misc.as<uint8_t>(), st));
-      if (timed) HIP_TRY(hipEventRecord(w->ev[3], st));
-      HIP_TRY(hipMemcpyAsync(out + c0 * n_bytes, w->misc.p, cc * n_bytes, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-    } else {
-      hh.resize((size_t)mnn.S * chunk);
-      limbs.resize((size_t)mnn.S);
-      if (timed) HIP_TRY(hipEventRecord(w->ev[3], st));
-      HIP_TRY(hipMemcpyAsync(hh.data(), H, hh.size() * 4, hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      for (size_t r = 0; r < cc; ++r) {
-        for (int l = 0; l < mnn.S; ++l) limbs[(size_t)l] = hh[(size_t)l * chunk + r];
-        if (!bn::to_be(mnn.value(limbs.data()), out + (c0 + r) * n_bytes, n_bytes))
-          return fail(DDS_E_RANGE, "result does not fit");
-      }
-    }
-    if (timed) {  // the chunk's kernels, first repack to egress (the copy to the host is not counted)
-      float ms = 0;
-      HIP_TRY(hipEventElapsedTime(&ms, w->ev[2], w->ev[3]));
-      kernel_ms += ms;
-    }
-  }
-  uint32_t flags = 0;
-  HIP_TRY(read_sync(w, st, fl, &flags, 4));
-  if (timed) {
-    std::lock_guard<std::mutex> lk(ctx->tmu);
-    ctx->total_ms += kernel_ms;
-    ctx->fold_ms += ladder_ms;
-    ctx->fold_launches += ladders;
-  }
-  if (flags & 2u) return fail(DDS_E_RANGE, "ciphertext not coprime to n");
-  if (flags & 1u) return fail(DDS_E_RANGE, "ciphertext does not fit the CRT halves");
-  return DDS_OK;
-}
-}  // namespace
-
-int dds_paillier_encrypt_batch(dds_ctx* ctx, const uint8_t* n_be, size_t n_bytes, const uint8_t* g_be, size_t g_bytes,
-                               const uint32_t* m, const uint8_t* r_be, size_t r_width, size_t count, uint8_t* out,
-                               size_t nsq_bytes) {
-  try {
-    if (!ctx || !n_be || !g_be || r_width == 0 || (count && (!m || !r_be || !out))) return fail(DDS_E_ARG, "bad args");
-    if (count == 0) return DDS_OK;
-    bn::Limbs n = bn::from_be(n_be, n_bytes);
-    bn::Limbs nsq = bn::mul(n, n);
-    if (nsq_bytes < bn::byte_length(nsq)) return fail(DDS_E_BUFSIZE, "nsq_bytes too small");
-    std::vector<uint8_t> nsq_be(bn::byte_length(nsq));
-    bn::to_be(nsq, nsq_be.data(), nsq_be.size());
-    std::shared_ptr<ModConsts> mc;
-    int rc = get_mod(ctx, nsq_be.data(), nsq_be.size(), &mc);
-    if (rc) return rc;
-    bn::Limbs g = bn::from_be(g_be, g_bytes);
-    if ((rc = check_rows(*mc, count))) return rc;
-    WorkerLease wl(ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    const int S = mc->S;
-    const size_t stride = round_up(count, 64);
-    HIP_TRY(w->x.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->x2.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->misc.ensure(count * 4));
-    if ((rc = ingest(ctx, w, wl.st, *mc, r_be, r_width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
-    HIP_TRY(hipMemcpyAsync(w->misc.p, m, count * 4, hipMemcpyHostToDevice, wl.st));
-    if ((rc = encrypt_device(w, wl.st, *mc, n, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
-                             w->x2.as<uint32_t>(), stride, true)))
-      return rc;
-    std::vector<uint32_t> h((size_t)S * stride);
-    HIP_TRY(hipMemcpy(h.data(), w->x2.p, h.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> limbs(S);
-    for (size_t i = 0; i < count; ++i) {
-      for (int l = 0; l < S; ++l) limbs[l] = h[(size_t)l * stride + i];
-      if (!bn::to_be(mc->value(limbs.data()), out + i * nsq_bytes, nsq_bytes))
-        return fail(DDS_E_RANGE, "result does not fit");
-    }
-    return DDS_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
-int dds_modexp_batch(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, const uint8_t* exp_be, size_t exp_bytes,
-                     const uint8_t* bases_be, size_t width, size_t count, uint8_t* out) {
-  try {
-    if (!ctx || !exp_be || width == 0 || (count && (!bases_be || !out))) return fail(DDS_E_ARG, "bad arguments");
-    if (count == 0) return DDS_OK;
-    std::shared_ptr<ModConsts> mc;
-    int rc = get_mod(ctx, mod_be, mod_bytes, &mc);
-    if (rc) return rc;
-    bn::Limbs e = bn::from_be(exp_be, exp_bytes);
-    if ((rc = check_rows(*mc, count))) return rc;
-    WorkerLease wl(ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    const int S = mc->S;
-    const size_t stride = round_up(count, 64);
-    HIP_TRY(w->x.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->x2.ensure((size_t)S * stride * 4));
-    if ((rc = ingest(ctx, w, wl.st, *mc, bases_be, width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
-    if ((rc = modexp_device(w, wl.st, *mc, e, nullptr, w->x.as<uint32_t>(), stride, nullptr, count,
-                            w->x2.as<uint32_t>(), stride)))
-      return rc;
-    std::vector<uint32_t> h((size_t)S * stride);
-    HIP_TRY(hipMemcpyAsync(h.data(), w->x2.p, h.size() * 4, hipMemcpyDeviceToHost, wl.st));
-    HIP_TRY(hipStreamSynchronize(wl.st));
-    std::vector<uint32_t> limbs(S);
-    for (size_t i = 0; i < count; ++i) {
-      for (int l = 0; l < S; ++l) limbs[l] = h[(size_t)l * stride + i];
-      if (!bn::to_be(mc->value(limbs.data()), out + i * mod_bytes, mod_bytes))
-        return fail(DDS_E_RANGE, "result does not fit");
-    }
-    return DDS_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
-static uint64_t splitmix64_host(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-int dds_col_fill_paillier_synth(dds_col* col, const uint8_t* n_be, size_t n_bytes, const uint8_t* g_be,
-                                size_t g_bytes, uint64_t seed, uint64_t row0, size_t count, uint32_t pool_size) {
-  return ddshe::host::col_fill_paillier_synth(col, n_be, n_bytes, g_be, g_bytes, seed, row0, count, pool_size, 1, 0);
-}
-
-}  // extern "C"
-
-namespace ddshe {
-namespace host {
-int col_fill_paillier_synth(dds_col* col, const uint8_t* n_be, size_t n_bytes, const uint8_t* g_be, size_t g_bytes,
-                            uint64_t seed, uint64_t row0, size_t count, uint32_t pool_size, uint32_t shards,
-                            uint32_t shard) {
-  try {
-    if (!col || !n_be || !g_be || pool_size == 0 || shards == 0 || shard >= shards) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
-    if (col->count + count > col->capacity) return fail(DDS_E_ARG, "column capacity exceeded");
-    ModConsts& mc = *col->mc;
-    bn::Limbs n = bn::from_be(n_be, n_bytes), g = bn::from_be(g_be, g_bytes);
-    if (bn::cmp(bn::mul(n, n), mc.N) != 0) return fail(DDS_E_ARG, "column modulus is not n^2");
-    const int S = mc.S;
-    const uint32_t tcount = 10000;  // DDSDataGenerator.scala:274 Random.nextInt(10000)
-    WorkerLease wl(col->ctx);
-    int rc;
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    hipStream_t st = wl.st;
-    // table T[m] = g^m (encrypt kernel with r = 1 and exponent n disabled)
-    const size_t ts = round_up(tcount, 64), ps = round_up(pool_size, 64);
-    HIP_TRY(w->misc.ensure((size_t)S * ts * 4));                      // T
-    HIP_TRY(w->misc2.ensure((size_t)S * ps * 4 * 2));                 // pool (plain) + pool (Montgomery)
-    HIP_TRY(w->x.ensure((size_t)S * std::max(ts, ps) * 4));           // r column
-    HIP_TRY(w->in2.ensure((size_t)std::max(ts, ps) * 4));             // exponents m
-    std::vector<uint32_t> ones((size_t)S * ts, 0), ms(ts, 0);
-    for (size_t i = 0; i < ts; ++i) ones[i] = 1;  // limb 0 = 1
-    for (uint32_t i = 0; i < tcount; ++i) ms[i] = i;
-    HIP_TRY(hipMemcpyAsync(w->x.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(w->in2.p, ms.data(), ms.size() * 4, hipMemcpyHostToDevice, st));
-    if ((rc = encrypt_device(w, st, mc, n, g, w->in2.as<uint32_t>(), w->x.as<uint32_t>(), ts, tcount,
-                             w->misc.as<uint32_t>(), ts, false)))
-      return rc;
-    // pool P_j = r_j^n (encrypt with m = 0), r_j from seed
-    std::vector<uint32_t> rcol((size_t)S * ps, 0), zeros(ps, 0);
-    for (uint32_t j = 0; j < pool_size; ++j) {
-      bn::Limbs r(n.size(), 0);
-      for (size_t q = 0; q < r.size(); ++q)
-        r[q] = (uint32_t)splitmix64_host(seed * 0x100000001B3ull + ((uint64_t)j << 20) + q);
-      bn::trim(r);
-      r = bn::mod(r, n);
-      if (r.empty()) r = bn::Limbs{1};
-      auto rl = mc.rw(r);
-      for (int l = 0; l < S; ++l) rcol[(size_t)l * ps + j] = rl[l];
-    }
-    HIP_TRY(hipMemcpyAsync(w->x.p, rcol.data(), rcol.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(w->in2.p, zeros.data(), zeros.size() * 4, hipMemcpyHostToDevice, st));
-    uint32_t* pool_plain = w->misc2.as<uint32_t>();
-    uint32_t* pool_mont = pool_plain + (size_t)S * ps;
-    if ((rc = encrypt_device(w, st, mc, n, g, w->in2.as<uint32_t>(), w->x.as<uint32_t>(), ps, pool_size,
-                             pool_plain, ps, true)))
-      return rc;
-    // Montgomery form P*R mod N = pairs(P, R mod N)
-    std::vector<uint32_t> rmod_col((size_t)S * ps, 0);
-    for (int l = 0; l < S; ++l)
-      for (size_t j = 0; j < ps; ++j) rmod_col[(size_t)l * ps + j] = mc.host[(size_t)kConstRmod * S + l];
-    HIP_TRY(hipMemcpyAsync(w->x.p, rmod_col.data(), rmod_col.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_pairs(S, pool_plain, w->x.as<uint32_t>(), ps, pool_size, mc.d, mc.n0, pool_mont, st));
-    HIP_TRY(launch_synth_rows(S, w->misc.as<uint32_t>(), ts, tcount, pool_mont, ps, pool_size, seed, row0, count, mc.d,
-                              mc.n0, col->d + col->count, col->stride, st, shards, shard));
-    HIP_TRY(hipStreamSynchronize(st));
-    col->count += count;
-    return DDS_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-}  // namespace host
-}  // namespace ddshe
-
-extern "C" {
-
-int dds_paillier_encrypt_batch_crt(dds_ctx* ctx, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be,
-                                   size_t q_bytes, const uint8_t* g_be, size_t g_bytes, const uint32_t* m,
-                                   const uint8_t* r_be, size_t r_width, size_t count, uint8_t* out, size_t nsq_bytes) {
-  try {
-    if (!ctx || !p_be || !q_be || !g_be || r_width == 0 || (count && (!m || !r_be || !out)))
-      return fail(DDS_E_ARG, "bad args");
-    if (count == 0) return DDS_OK;
-    std::shared_ptr<CrtKey> k;
-    int rc = get_crt_key(ctx, bn::from_be(p_be, p_bytes), bn::from_be(q_be, q_bytes), &k);
-    if (rc) return rc;
-    ModConsts& mn = *k->mn;
-    if (nsq_bytes < mn.bytes) return fail(DDS_E_BUFSIZE, "nsq_bytes too small");
-    for (size_t i = 0; i < count; ++i) {  // r in [1, n): the CRT halves need r < 2^bits(n)
-      bn::Limbs r = bn::from_be(r_be + i * r_width, r_width);
-      if (r.empty() || bn::cmp(r, k->n) >= 0) return fail(DDS_E_RANGE, "r must be in [1, n)");
-    }
-    const bn::Limbs g = bn::from_be(g_be, g_bytes);
-    if ((rc = check_rows(mn, count))) return rc;
-    WorkerLease wl(ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    const int S = mn.S;
-    const size_t stride = round_up(count, 64);
-    HIP_TRY(w->x.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->x2.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->misc.ensure(count * 4));
-    if ((rc = ingest(ctx, w, wl.st, mn, r_be, r_width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
-    HIP_TRY(hipMemcpyAsync(w->misc.p, m, count * 4, hipMemcpyHostToDevice, wl.st));
-    if (crt_fits(*k))
-      rc = encrypt_crt_device(w, wl.st, *k, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
-                              w->x2.as<uint32_t>(), stride);
-    else  // unbalanced factors: public-key path (same result)
-      rc = encrypt_device(w, wl.st, mn, k->n, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
-                          w->x2.as<uint32_t>(), stride, true);
-    if (rc) return rc;
-    std::vector<uint32_t> h((size_t)S * stride);
-    HIP_TRY(hipMemcpy(h.data(), w->x2.p, h.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<uint32_t> limbs(S);
-    for (size_t i = 0; i < count; ++i) {
-      for (int l = 0; l < S; ++l) limbs[l] = h[(size_t)l * stride + i];
-      if (!bn::to_be(mn.value(limbs.data()), out + i * nsq_bytes, nsq_bytes))
-        return fail(DDS_E_RANGE, "result does not fit");
-    }
-    return DDS_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
 int dds_col_fill_table_synth(dds_col* col, const uint8_t* table_be, size_t width, size_t tcount, uint64_t seed,
                              uint64_t row0, size_t count) {
   try {
@@ -2603,95 +1969,7 @@ int dds_col_fill_random(dds_col* col, size_t bits, uint64_t seed, uint64_t row0,
   }
 }
 
-int dds_col_encrypt_paillier(dds_col* out, dds_col* rcol, size_t r_first, const uint32_t* d_m, size_t count,
-                             const uint8_t* n_be, size_t n_bytes, const uint8_t* g_be, size_t g_bytes,
-                             const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be, size_t q_bytes) {
-  try {
-    if (!out || !rcol || !n_be || !g_be || (count && !d_m) || (!p_be) != (!q_be)) return fail(DDS_E_ARG, "bad args");
-    if (count == 0) return DDS_OK;
-    if (r_first + count > rcol->count) return fail(DDS_E_ARG, "r rows out of range");
-    std::unique_lock<std::shared_mutex> lk(out->mu, std::defer_lock);
-    std::unique_lock<std::shared_mutex> lr(rcol->mu, std::defer_lock);
-    if (out == rcol) return fail(DDS_E_ARG, "out and r columns must differ");
-    std::lock(lk, lr);
-    if (out->count + count > out->capacity) return fail(DDS_E_ARG, "column capacity exceeded");
-    const bn::Limbs n = bn::from_be(n_be, n_bytes), g = bn::from_be(g_be, g_bytes);
-    const bn::Limbs nsq = bn::mul(n, n);
-    if (bn::cmp(nsq, out->mc->N) != 0 || bn::cmp(nsq, rcol->mc->N) != 0)
-      return fail(DDS_E_ARG, "columns must be over n^2");
-    std::shared_ptr<CrtKey> k;
-    int rc;
-    if (p_be) {
-      if ((rc = get_crt_key(out->ctx, bn::from_be(p_be, p_bytes), bn::from_be(q_be, q_bytes), &k))) return rc;
-      if (bn::cmp(k->n, n) != 0) return fail(DDS_E_ARG, "p*q != n");
-    }
-    WorkerLease wl(out->ctx);
-    if ((rc = wl.acquire())) return rc;
-    uint32_t* dst = out->d + out->count;
-    const uint32_t* r = rcol->d + r_first;
-    if (k && crt_fits(*k))
-      rc = encrypt_crt_device(wl.w, wl.st, *k, g, d_m, r, rcol->stride, count, dst, out->stride);
-    else
-      rc = encrypt_device(wl.w, wl.st, *out->mc, n, g, d_m, r, rcol->stride, count, dst, out->stride, true);
-    if (rc) return rc;
-    out->count += count;
-    return DDS_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
-int dds_paillier_decrypt_batch_crt(dds_ctx* ctx, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be,
-                                   size_t q_bytes, const uint8_t* g_be, size_t g_bytes, const uint8_t* c_be,
-                                   size_t width, size_t count, uint8_t* out, size_t n_bytes) {
-  try {
-    if (!ctx || !p_be || !q_be || !g_be || (count && (!c_be || !out || width == 0))) return fail(DDS_E_ARG, "bad args");
-    if (count == 0) return DDS_OK;
-    std::shared_ptr<CrtKey> k;
-    int rc = get_crt_key(ctx, bn::from_be(p_be, p_bytes), bn::from_be(q_be, q_bytes), &k);
-    if (rc) return rc;
-    if (n_bytes < bn::byte_length(k->n)) return fail(DDS_E_BUFSIZE, "n_bytes too small");
-    std::shared_ptr<DecKey> dk;
-    if ((rc = get_dec_key(ctx, *k, bn::from_be(g_be, g_bytes), &dk))) return rc;
-    ModConsts& mn = *k->mn;
-    for (size_t i = 0; i < count; ++i)
-      if (bn::cmp(bn::from_be(c_be + i * width, width), mn.N) >= 0) return fail(DDS_E_RANGE, "c must be in [0, n^2)");
-    if ((rc = check_rows(mn, count))) return rc;
-    WorkerLease wl(ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    const size_t stride = round_up(count, 64);
-    HIP_TRY(w->x.ensure((size_t)mn.S * stride * 4));
-    if ((rc = ingest(ctx, w, wl.st, mn, c_be, width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
-    return decrypt_crt_device(ctx, w, wl.st, *k, *dk, w->x.as<uint32_t>(), stride, count, out, n_bytes);
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
-int dds_col_decrypt_paillier(dds_col* col, size_t first, size_t count, const uint8_t* p_be, size_t p_bytes,
-                             const uint8_t* q_be, size_t q_bytes, const uint8_t* g_be, size_t g_bytes, uint8_t* out,
-                             size_t n_bytes) {
-  try {
-    if (!col || !p_be || !q_be || !g_be || (count && !out)) return fail(DDS_E_ARG, "bad args");
-    std::shared_lock<std::shared_mutex> lk(col->mu);
-    if (first + count > col->count) return fail(DDS_E_ARG, "rows out of range");
-    if (count == 0) return DDS_OK;
-    std::shared_ptr<CrtKey> k;
-    int rc = get_crt_key(col->ctx, bn::from_be(p_be, p_bytes), bn::from_be(q_be, q_bytes), &k);
-    if (rc) return rc;
-    if (bn::cmp(k->mn->N, col->mc->N) != 0) return fail(DDS_E_ARG, "column modulus is not (p*q)^2");
-    if (col->mc->S != k->mn->S || col->mc->W != k->mn->W) return fail(DDS_E_UNSUPPORTED, "column limb layout");
-    if (n_bytes < bn::byte_length(k->n)) return fail(DDS_E_BUFSIZE, "n_bytes too small");
-    std::shared_ptr<DecKey> dk;
-    if ((rc = get_dec_key(col->ctx, *k, bn::from_be(g_be, g_bytes), &dk))) return rc;
-    WorkerLease wl(col->ctx);
-    if ((rc = wl.acquire())) return rc;
-    return decrypt_crt_device(col->ctx, wl.w, wl.st, *k, *dk, col->d + first, col->stride, count, out, n_bytes);
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
+// ---- modular exponentiation, Paillier encryption / decryption: ddshe_paillier.cpp --------
 
 // ---- OPE filter ------------------------------------------------------------------
 int dds_ope_filter_device(dds_ctx* ctx, const int64_t* d_col, const uint8_t* d_valid, size_t n, int64_t bound, int op,

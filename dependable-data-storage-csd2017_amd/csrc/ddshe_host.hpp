@@ -1,4 +1,5 @@
-// Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_opecol.cpp, ddshe_mctx.cpp):
+// Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_opecol.cpp,
+// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp):
 // contexts, stream/buffer pools, per-modulus Montgomery constants, device columns and the
 // orchestration helpers around the HIP kernels. Not part of the public ABI (include/ddshe.h).
 #pragma once
@@ -99,7 +100,7 @@ struct Worker {
   DevBuf sflags;            // string scans' row flags, zero between scans when sflags_zero
   bool sflags_zero = false;
   hipEvent_t ev_done = {};
-  DevBuf crt[7];  // CRT encryption scratch (see encrypt_crt_device)
+  DevBuf crt[7];  // CRT scratch of Paillier encryption and decryption (encrypt_crt_device, decrypt_crt_device)
   hipEvent_t ev[4] = {};
   // decimal codec: double-buffered pinned chunks (chars, offsets), their device copies,
   // per-row status bytes, and the event after each slot's last use
@@ -230,7 +231,7 @@ struct PairQueue;  // ddshe_pairs.cpp
 }  // namespace ddshe
 
 
-struct CrtKey;  // CRT form of a Paillier key (encrypt_crt_device)
+struct CrtKey;  // CRT form of a Paillier key (ddshe_paillier.cpp)
 
 struct dds_ctx {
   int device = 0;
@@ -433,7 +434,6 @@ struct WorkerLease {
 };
 
 
-// Upload `count` big-endian operands into an rW column (X, stride) validated against mc.
 // Host worker pool for the boundary codecs: parallel copies of caller buffers into pinned staging
 // (one thread copies ~10-15 GB/s, below what PCIe moves). parallel_for(n, f) splits [0, n) into
 // one contiguous slice per thread, aligned to `align`, and calls f(begin, end) on each.
@@ -548,7 +548,6 @@ int get_mod(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, std::shared_p
 int modmul_fold_be(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, size_t min_bits, const uint8_t* ops,
                    size_t width, size_t count, uint8_t* out, size_t out_cap, size_t* out_len);
 int product_tree(dds_ctx* ctx, const std::vector<uint32_t>& h, size_t count, size_t len, size_t cap16, bn::Limbs* out);
-bn::Limbs low_bits(const bn::Limbs& x, size_t t);
 int fold_even_modulus(dds_ctx* ctx, const bn::Limbs& M, const std::vector<bn::Limbs>& xs, const std::vector<bool>& negs,
                       bn::Limbs* out);
 void record_time(dds_ctx* ctx, Worker* w, hipStream_t st, bool begin, int slot);
@@ -585,6 +584,13 @@ int fold_partial_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, 
                         const uint32_t* d_ids = nullptr);
 void account_fold(dds_ctx* ctx, Worker* w);
 int emit_be(const bn::Limbs& v, size_t width, uint8_t* out, size_t out_cap, size_t* out_len);
+// rows of an rW column (shape of mc) -> `width`-byte big-endian rows at `out` (host). reduce: rows are
+// < 2N and get N subtracted when >= N; otherwise they are canonical. width >= mc.bytes (callers check).
+// Shapes of up to kEgressMaxLimbs limbs are serialised on the GPU (w->misc as device staging, pieces of
+// <= 256 MiB), wider ones on the host. Synchronises the stream. before_copy (optional) is recorded after
+// the last kernel and before the first device-to-host copy.
+int rows_to_be(Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride, size_t count,
+               bool reduce, uint8_t* out, size_t width, hipEvent_t before_copy = nullptr);
 // Upload `count` big-endian operands into an rW column (X, stride) validated against mc; rows >= 2N
 // are reduced on the GPU and, when `reduced` is given, listed there (ascending).
 int ingest(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint8_t* ops, size_t width, size_t count,

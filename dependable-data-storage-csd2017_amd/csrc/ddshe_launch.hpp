@@ -1,4 +1,5 @@
-// Internal launcher interface between the C-ABI (ddshe_capi.cpp) and the HIP kernels.
+// Internal launcher interface between the C-ABI's host code (ddshe_capi.cpp, ddshe_paillier.cpp,
+// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
