@@ -9,14 +9,17 @@ using namespace ddshe;
 using namespace ddshe::host;
 
 // Decryption constants of one (p, q, g) (decrypt_crt_device), built on the first decrypt with that g, so
-// encrypt-only users pay nothing. For factor i of (p, q), at d + off[i], in the limbs of its square's shape:
+// encrypt-only users pay nothing. md[i] holds d^2 for factor i of (p, q): the key's own constants (CrtKey::mp,
+// mq) where the halves of c fit their shape, else a copy in the next shape that holds them (get_dec_key).
+// For factor i, at d + off[i], in the limbs of md[i]'s shape:
 //   2^(j W_n)·R_d | R_d (mod d^2): x_d = c mod d^2 from the halves of c split at limb j of the n^2 layout
 //   h_d·R_d | d^2 - h_d, with h_d = L_d(g^(d-1) mod d^2)^-1 mod d
 //   d^-1 mod 2^(sdiv W_d), sdiv = ceil((bits(d) + 1) / W_d) limbs (the exact division by d)
 // (S_d limbs each, d the factor); then, at d + off_e, e_p·R_n | e_q·R_n (mod n) in the limbs of n's shape.
 struct DecKey {
-  std::shared_ptr<ModConsts> mnn;  // modulus n: the recombination and the plaintexts' layout
-  bn::Limbs e[2];                  // p - 1, q - 1
+  std::shared_ptr<ModConsts> mnn;    // modulus n: the recombination and the plaintexts' layout
+  std::shared_ptr<ModConsts> md[2];  // p^2, q^2 in shapes that hold the halves of c
+  bn::Limbs e[2];                    // p - 1, q - 1
   int j = 0, sdiv[2] = {0, 0};
   size_t off[2] = {0, 0}, off_e = 0;
   uint32_t* d = nullptr;
@@ -174,6 +177,10 @@ int encrypt_crt_device(Worker* w, hipStream_t st, CrtKey& k, const bn::Limbs& g,
   return DDS_OK;
 }
 
+// how far beyond bits(d^2) a half of c may reach and still have d^2 moved to a wider shape (get_dec_key): twice
+// the W_n + 2 bits that limb rounding costs factors of equal length, so lengths up to 35 bits apart always pass
+constexpr size_t kDecWidenBits = 64;
+
 int get_dec_key(dds_ctx* ctx, CrtKey& k, const bn::Limbs& g, std::shared_ptr<DecKey>* out) {
   {
     std::lock_guard<std::mutex> lk(k.dmu);
@@ -186,16 +193,25 @@ int get_dec_key(dds_ctx* ctx, CrtKey& k, const bn::Limbs& g, std::shared_ptr<Dec
   auto dk = std::make_shared<DecKey>();
   const ModConsts& mn = *k.mn;
   // Shape check (as crt_fits for encrypt): c, a row of the n^2 layout below 2 n^2, splits at limb j into
-  // c_lo (j W_n bits) and c_hi; both must fit the limbs of p^2 and of q^2 with the usual 2 bits to spare
+  // c_lo (j W_n bits) and c_hi; both must fit the limbs of p^2 and of q^2 with the usual 2 bits to spare.
+  // The split falls on a limb, so a half is up to W_n + 2 bits longer than the square of a factor half as
+  // long as n: a d^2 that fills its own shape to within those bits (two 559-bit primes: 1118 of 40 x 28 - 2)
+  // is taken in the next shape that holds the halves. Only for such a shortfall of limb rounding, at most
+  // kDecWidenBits beyond bits(d^2); a half further out means factors of different lengths, and is refused.
   const size_t cbits = mn.bits + 1;
   dk->j = (int)((cbits + 2 * (size_t)mn.W - 1) / (2 * (size_t)mn.W));
-  const size_t lo = (size_t)dk->j * mn.W, hi = cbits > lo ? cbits - lo : 0;
-  for (const ModConsts* md : {k.mp.get(), k.mq.get()}) {
-    const size_t cap = (size_t)md->S * md->W - 2;
-    if (dk->j < 1 || dk->j >= mn.S || lo > cap || hi > cap)
-      return fail(DDS_E_ARG, "factors too unbalanced for CRT decrypt");
-  }
+  const size_t lo = (size_t)dk->j * mn.W, hi = cbits > lo ? cbits - lo : 0, half = std::max(lo, hi);
+  if (dk->j < 1 || dk->j >= mn.S) return fail(DDS_E_ARG, "factors too unbalanced for CRT decrypt");
   int rc;
+  for (int i = 0; i < 2; ++i) {
+    dk->md[i] = i ? k.mq : k.mp;
+    const ModConsts& own = *dk->md[i];
+    if (half <= (size_t)own.S * own.W - 2) continue;
+    if (half > own.bits + kDecWidenBits) return fail(DDS_E_ARG, "factors too unbalanced for CRT decrypt");
+    std::vector<uint8_t> b(bn::byte_length(own.N));
+    bn::to_be(own.N, b.data(), b.size());
+    if ((rc = get_mod(ctx, b.data(), b.size(), &dk->md[i], half))) return rc;
+  }
   {
     std::vector<uint8_t> nb(bn::byte_length(k.n));
     bn::to_be(k.n, nb.data(), nb.size());
@@ -206,7 +222,7 @@ int get_dec_key(dds_ctx* ctx, CrtKey& k, const bn::Limbs& g, std::shared_ptr<Dec
   std::vector<uint32_t> host;
   auto put = [&](const std::vector<uint32_t>& v) { host.insert(host.end(), v.begin(), v.end()); };
   const bn::Limbs* ds[2] = {&k.p, &k.q};
-  const ModConsts* mds[2] = {k.mp.get(), k.mq.get()};
+  const ModConsts* mds[2] = {dk->md[0].get(), dk->md[1].get()};
   for (int i = 0; i < 2; ++i) {
     const bn::Limbs& d = *ds[i];
     const ModConsts& md = *mds[i];
@@ -258,7 +274,7 @@ int get_dec_key(dds_ctx* ctx, CrtKey& k, const bn::Limbs& g, std::shared_ptr<Dec
 int decrypt_crt_device(dds_ctx* ctx, Worker* w, hipStream_t st, CrtKey& k, DecKey& dk, const uint32_t* d_c,
                        size_t cstride, size_t count, uint8_t* out, size_t n_bytes) {
   ModConsts &mn = *k.mn, &mnn = *dk.mnn;
-  ModConsts* mds[2] = {k.mp.get(), k.mq.get()};
+  ModConsts* mds[2] = {dk.md[0].get(), dk.md[1].get()};
   const size_t chunk = std::min<size_t>(round_up(count, 64), (size_t)1 << 18);
   const size_t sh = (size_t)std::max(mds[0]->S, mds[1]->S) * chunk * 4, sn = (size_t)mnn.S * chunk * 4;
   const size_t sizes[6] = {sh, sh, sh, sn, sn, sn};

@@ -411,6 +411,12 @@ int dds_paillier_encrypt_batch_crt(dds_ctx* ctx, const uint8_t* p_be, size_t p_b
  * q^2 (exponents p-1, q-1), L function and recombination on the device; equals L(c^lambda mod n^2) mu mod n.
  * n_bytes below the byte length of n: DDS_E_BUFSIZE; p, q not distinct odd primes, a g whose
  * L(g^(d-1) mod d^2) is not invertible, or factors too unbalanced for the half-width limbs: DDS_E_ARG.
+ * "Too unbalanced", exactly: c (below 2 n^2, B = bits(n^2) + 1 bits) is split at limb j = ceil(B / 2W) of
+ * the n^2 layout (W = 27 or 28 bits per limb) into halves of jW and B - jW bits; with h the longer of the
+ * two, each factor d needs h <= S_d W_d - 2 for the limb shape of d^2, or else h <= bits(d^2) + 64, in
+ * which case d^2 is computed in the next wider shape that holds h. Factors whose bit lengths differ by at
+ * most 35 always pass (h <= bits(d^2) + 64 then); a wider gap passes where the shape of the smaller
+ * factor's square has the room (600 + 420 bits does, 1536 + 512 bits does not).
  * After an error the contents of out are unspecified. With dds_ctx_set_timing on, a decrypt call adds
  * the device time of its kernels to total_ms and that of its exponentiation ladders to fold_ms. */
 int dds_paillier_decrypt_batch_crt(dds_ctx*, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be, size_t q_bytes,

@@ -548,6 +548,31 @@ def gen_prime(bits: int, rng: random.Random) -> int:
             return c
 
 
+def paillier_key_from_factors(p: int, q: int, g: int) -> dict:
+    """The key dict of (p, q, g): lambda = lcm(p-1, q-1), mu = L(g^lambda mod n^2)^-1 mod n. ValueError when
+    that inverse does not exist (g is not a valid Paillier generator for n)."""
+    n = p * q
+    nsq = n * n
+    lam = (p - 1) * (q - 1) // math.gcd(p - 1, q - 1)
+    if math.gcd(g, n) != 1:
+        raise ValueError("g is not coprime to n")
+    L = (pow(g, lam, nsq) - 1) // n
+    if math.gcd(L, n) != 1:
+        raise ValueError("L(g^lambda mod n^2) is not invertible mod n")
+    return {"g": g, "lambda": lam, "mu": pow(L, -1, n), "n": n, "nsquare": nsq, "p": p, "q": q}
+
+
+def _random_g(p: int, q: int, rng: random.Random) -> dict:
+    """A random valid g in Z*_{n^2} for (p, q), drawn as gen_paillier_key always has."""
+    nsq = (p * q) ** 2
+    while True:
+        g = rng.randrange(2, nsq)
+        try:
+            return paillier_key_from_factors(p, q, g)
+        except ValueError:
+            continue
+
+
 def gen_paillier_key(bits: int, seed: int) -> dict:
     """Paillier key with an n of exactly ``bits`` bits and a random g ∈ Z*_{n²}
     (like the committed key, whose g is random: SURVEY.md F6)."""
@@ -558,17 +583,41 @@ def gen_paillier_key(bits: int, seed: int) -> dict:
         n = p * q
         if p != q and n.bit_length() == bits and math.gcd(n, (p - 1) * (q - 1)) == 1:
             break
-    nsq = n * n
-    lam = (p - 1) * (q - 1) // math.gcd(p - 1, q - 1)
+    return _random_g(p, q, rng)
+
+
+def gen_paillier_key_sizes(pbits: int, qbits: int, seed: int) -> dict:
+    """Paillier key from a ``pbits``-bit and a ``qbits``-bit prime (top two bits set, as gen_prime draws
+    them): the same prime test, gcd condition and g loop as gen_paillier_key, without its constraint on
+    the length of n."""
+    rng = random.Random(seed)
     while True:
-        g = rng.randrange(2, nsq)
-        if math.gcd(g, n) != 1:
-            continue
-        L = (pow(g, lam, nsq) - 1) // n
-        if math.gcd(L, n) == 1:
-            mu = pow(L, -1, n)
+        p = gen_prime(pbits, rng)
+        q = gen_prime(qbits, rng)
+        if p != q and math.gcd(p * q, (p - 1) * (q - 1)) == 1:
             break
-    return {"g": g, "lambda": lam, "mu": mu, "n": n, "nsquare": nsq, "p": p, "q": q}
+    return _random_g(p, q, rng)
+
+
+def paillier_edge_rows(key: dict, seed: int) -> list:
+    """(m, r) pairs at the plaintexts where a CRT decryption can go wrong: m a multiple of one factor
+    (m_p = 0 or m_q = 0), next to one, at the ends of [0, n), and on the limb boundaries of the 27- and
+    28-bit layouts (limbs 1, 2 and the last below n); r cycles through 1 (c = g^m; with m = 0, c = 1),
+    n - 1 and one seeded random unit of Z_n, so every m appears once and every r in a third of the rows."""
+    p, q, n = key["p"], key["q"], key["n"]
+    ms = [0, 1, p - 1, p, p + 1, q - 1, q, q + 1, 2 * p, n - p, n - q, n - 1, p * (q - 1), q * (p - 1)]
+    for w in (27, 28):
+        top = (n.bit_length() - 1) // w  # 2^(w top) <= 2^(bits(n) - 1) < n
+        for i in (1, 2, top):
+            ms += [2 ** (w * i) - 1, 2 ** (w * i)]
+    ms = [m for i, m in enumerate(ms) if 0 <= m < n and m not in ms[:i]]
+    rng = random.Random(seed)
+    while True:
+        ru = rng.randrange(2, n - 1)
+        if math.gcd(ru, n) == 1:
+            break
+    rs = (1, n - 1, ru)
+    return [(m, rs[i % 3]) for i, m in enumerate(ms)]
 
 
 def gen_rsa_key(bits: int, seed: int, e: int = 65537) -> dict:
