@@ -22,6 +22,7 @@
 #include <thread>
 #include <vector>
 
+#include "ddshe_dec10.hpp"
 #include "ddshe_host.hpp"
 
 using namespace ddshe;
@@ -553,7 +554,104 @@ int rows_to_be(Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X
   return DDS_OK;
 }
 
+size_t dec_width(const ModConsts& mc) { return bn::to_dec(bn::sub(mc.N, bn::Limbs{1})).size(); }
 
+hipError_t copy_stream(Worker* w);
+
+int rows_to_dec(dds_ctx* ctx, Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride,
+                size_t count, bool reduce, char* chars, size_t chars_cap, uint64_t* offsets, size_t* chars_len) {
+  *chars_len = 0;
+  offsets[0] = 0;
+  if (count == 0) return DDS_OK;
+  const int S = mc.S;
+  const size_t width = dec_width(mc), bits = bn::bit_length(mc.N);
+  const uint32_t pitch = (uint32_t)round_up(width, 4);
+  // bounded device staging: two pieces in flight, each at most 96 MiB of fixed-pitch digits and as much for
+  // the packed rows. k_dec_print runs one lane per row, a one-wave block holds R rows, and its LDS admits
+  // a few blocks per CU (4 at 4096 bits): the chip converts cus * blocks * R rows at a time (64 Ki there)
+  // and a piece takes as long as its last, partly filled round, so a piece is a whole number of rounds
+  // where the staging allows one.
+  size_t piece = std::max<size_t>(1, std::min<size_t>(((size_t)96 << 20) / pitch, (size_t)1 << 20));
+  {
+    const size_t T = (size_t)dec10::row_words(bits, S), R = dec_print_rows((int)T);
+    const size_t per_cu = R ? std::min<size_t>(std::max<size_t>(((size_t)160 << 10) / ((T + 2) * R * 4), 1), 32) : 1;
+    const size_t round = (size_t)(ctx->cus > 0 ? ctx->cus : 256) * per_cu * R;
+    if (round && piece >= round) piece = piece / round * round;
+  }
+  if (const char* e = getenv("DDSHE_DEC_PIECE_ROWS")) {
+    const long long v = atoll(e);
+    if (v > 0) piece = (size_t)v;
+  }
+  piece = std::min(piece, count);
+  const size_t pieces = (count + piece - 1) / piece;
+  for (size_t s = 0; s < std::min<size_t>(pieces, 2); ++s) {
+    HIP_TRY(w->edig[s].ensure(piece * pitch));
+    HIP_TRY(w->echars[s].ensure(piece * pitch));
+    HIP_TRY(w->elens[s].ensure(piece * 4));
+    HIP_TRY(w->eoffs[s].ensure((piece + 1) * 8));
+  }
+  HIP_TRY(w->flags.ensure(16));
+  HIP_TRY(copy_stream(w));
+  hipStream_t cs = w->cstream;
+  uint32_t* hflag = nullptr;
+  HIP_TRY(stage_ptr(w, &hflag));
+  const uint32_t* nmod = reduce ? mc.d + (size_t)kConstN * S : nullptr;
+  const bool timed = ctx->timing.load();
+  // piece k's kernels into slot k & 1, on st; its offsets start at the end of piece k - 1, read on the device
+  auto launch = [&](size_t k) -> int {
+    const size_t b = k * piece, n = std::min(piece, count - b), s = k & 1;
+    uint32_t* flag = w->flags.as<uint32_t>() + s;
+    HIP_TRY(hipMemsetAsync(flag, 0, 4, st));
+    HIP_TRY(launch_dec_print(X + b, stride, n, S, mc.W, nmod, bits, pitch, w->edig[s].as<uint8_t>(),
+                             w->elens[s].as<uint32_t>(), flag, st));
+    HIP_TRY(launch_dec_offsets(w->elens[s].as<uint32_t>(), n, k ? w->eoffs[s ^ 1].as<uint64_t>() + piece : nullptr,
+                               w->eoffs[s].as<uint64_t>(), st));
+    HIP_TRY(launch_dec_pack(w->edig[s].as<uint8_t>(), pitch, w->elens[s].as<uint32_t>(), w->eoffs[s].as<uint64_t>(), n,
+                            w->echars[s].as<uint8_t>(), st));
+    HIP_TRY(hipEventRecord(w->ev_dec[s], st));
+    return DDS_OK;
+  };
+  int rc;
+  uint64_t base = 0;
+  bool fits = true;
+  for (size_t k = 0; k < pieces; ++k) {
+    const size_t b = k * piece, n = std::min(piece, count - b), s = k & 1;
+    if (k == 0 || timed) {
+      if (timed) HIP_TRY(hipEventRecord(w->ev[2], st));
+      if ((rc = launch(k))) return rc;
+      if (timed) HIP_TRY(hipEventRecord(w->ev[3], st));
+    }
+    // the next piece converts while this one is copied out; its slot's last copies (piece k - 1) are done
+    if (!timed && k + 1 < pieces && (rc = launch(k + 1))) return rc;
+    HIP_TRY(hipEventSynchronize(w->ev_dec[s]));
+    if (timed) {
+      float ms = 0;
+      if (hipEventSynchronize(w->ev[3]) == hipSuccess && hipEventElapsedTime(&ms, w->ev[2], w->ev[3]) == hipSuccess) {
+        std::lock_guard<std::mutex> lk(ctx->tmu);
+        ctx->total_ms += ms;
+      }
+    }
+    // offsets[b + n], this piece's end, is rewritten with the same value by the next piece's first entry
+    HIP_TRY(hipMemcpyAsync(offsets + b, w->eoffs[s].p, (n + 1) * 8, hipMemcpyDeviceToHost, cs));
+    HIP_TRY(hipMemcpyAsync(hflag, w->flags.as<uint32_t>() + s, 4, hipMemcpyDeviceToHost, cs));
+    HIP_TRY(hipStreamSynchronize(cs));
+    if (hflag[0]) {
+      (void)hipStreamSynchronize(st);
+      return fail(DDS_E_RANGE, "row not below the modulus: its decimal text does not fit");
+    }
+    const uint64_t end = offsets[b + n];
+    if (fits && end <= chars_cap) {
+      HIP_TRY(hipMemcpyAsync(chars + base, w->echars[s].p, (size_t)(end - base), hipMemcpyDeviceToHost, cs));
+      HIP_TRY(hipStreamSynchronize(cs));
+    } else {
+      fits = false;  // the remaining pieces are only measured
+    }
+    base = end;
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  *chars_len = (size_t)base;
+  return fits ? DDS_OK : fail(DDS_E_BUFSIZE, "chars buffer too small");
+}
 
 int ingest(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint8_t* ops, size_t width, size_t count,
            DevBuf& raw, uint32_t* X, size_t stride, std::vector<size_t>* reduced) {
@@ -1780,6 +1878,28 @@ int dds_col_read(dds_col* col, size_t first, size_t count, uint8_t* out) {
     if ((rc = wl.acquire())) return rc;
     // rows are kept < 2N: canonical residues out
     return rows_to_be(wl.w, wl.st, *col->mc, col->d + first, col->stride, count, true, out, col->mc->bytes);
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+size_t dds_col_dec_width(const dds_col* col) { return col ? dec_width(*col->mc) : 0; }
+
+int dds_col_read_dec(dds_col* col, size_t first, size_t count, char* chars, size_t chars_cap, uint64_t* offsets,
+                     size_t* chars_len) {
+  try {
+    if (!col || !offsets || !chars_len || (count && !chars)) return fail(DDS_E_ARG, "bad arguments");
+    std::shared_lock<std::shared_mutex> lk(col->mu);
+    if (first > col->count || count > col->count - first) return fail(DDS_E_ARG, "rows out of range");
+    *chars_len = 0;
+    offsets[0] = 0;
+    if (count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    int rc;
+    if ((rc = wl.acquire())) return rc;
+    // rows are kept < 2N: canonical residues out
+    return rows_to_dec(col->ctx, wl.w, wl.st, *col->mc, col->d + first, col->stride, count, true, chars, chars_cap,
+                       offsets, chars_len);
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");
   }

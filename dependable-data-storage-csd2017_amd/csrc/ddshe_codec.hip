@@ -21,9 +21,14 @@
 //      contiguous group layout, exact normalisation, 2N compare, store.
 // k_dec_fix: rows flagged negative (BigInteger.mod: x -> N - (|x| mod N)) or >= 2N
 // (x -> x mod N by two Montgomery products) are rewritten in place.
+//
+// The other direction (the text a PutSet carries, hlib's encrypt result printed by BigInteger.toString,
+// SJHomoLibProvider.scala:58): k_dec_print / k_dec_scan / k_dec_pack below turn column rows into the same
+// chars + offsets layout (rows_to_dec, ddshe_capi.cpp).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddshe_dec10.hpp"
 #include "ddshe_device.hpp"
 #include "ddshe_fold.hpp"
 #include "ddshe_launch.hpp"
@@ -267,6 +272,150 @@ __global__ void __launch_bounds__(256, 2) k_dec_fix(uint32_t* __restrict__ X, si
     for (int l = 0; l < L; ++l) a[l] = t[l];
   }
   g.store_col(a, X, stride, row);
+}
+
+// ---- egress: column rows -> BigInteger.toString text ------------------------------------------
+// k_dec_print, one wave per block of R rows (R sized from the modulus so the block's LDS stays within
+// 64 KiB): the rows' limbs are read limb-major into LDS (coalesced over rows, as k_egress_be), then one
+// lane per row subtracts N where the row is >= N, regroups the limbs into 32-bit words and peels
+// base-10^9 chunks (ddshe_dec10.hpp); the wave then prints the rows' digits right-aligned at a fixed
+// pitch, four per store, and one length per row. flags[0] |= 1 if a row's text would not fit the pitch
+// (a row that was not below 2N / N), whose length is then stored as 0.
+__global__ void __launch_bounds__(64) k_dec_print(const uint32_t* __restrict__ X, size_t stride, size_t count, int S,
+                                                  int W, const uint32_t* __restrict__ nmod, int nw, int T, int R,
+                                                  uint32_t pitch, uint32_t* __restrict__ dig4,
+                                                  uint32_t* __restrict__ lens, uint32_t* __restrict__ flags) {
+  extern __shared__ uint32_t sl[];  // T * R row words, then R chunk counts, then R lengths
+  const int tid = threadIdx.x;
+  const size_t r0 = (size_t)blockIdx.x * R;
+  const int nrows = (int)min((size_t)R, count - r0);
+  int* snc = reinterpret_cast<int*>(sl + (size_t)T * R);
+  uint32_t* slen = sl + (size_t)T * R + R;
+  if (tid < nrows) {
+    for (int l = 0; l < S; ++l) sl[(size_t)l * R + tid] = X[(size_t)l * stride + r0 + tid];
+    uint32_t* a = sl + tid;
+    if (nmod) dec10::canon_sub(a, R, S, W, nmod);
+    dec10::regroup32(a, R, S, W, nw);
+    int nc = dec10::peel(a, R, nw, T);
+    uint32_t len = nc < 0 ? pitch + 1 : dec10::text_len(a, R, T, nc);
+    if (len > pitch) {
+      atomicOr(flags, 1u);
+      len = 0;
+      nc = 0;
+    }
+    snc[tid] = nc;
+    slen[tid] = len;
+    lens[r0 + tid] = len;
+  }
+  __syncthreads();
+  const uint32_t pw = pitch / 4;  // pitch is a multiple of 4
+  for (int r = 0; r < nrows; ++r) {
+    const uint32_t len = slen[r];
+    const int nc = snc[r];
+    const uint32_t* a = sl + r;
+    uint32_t* o = dig4 + (r0 + r) * (size_t)pw;
+    for (uint32_t g = (pitch - len) / 4 + tid; g < pw; g += 64) {
+      uint32_t v = 0;
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t d = pitch - 1 - (4 * g + k);  // digit index from the right end
+        const uint32_t ch = d < len ? dec10::text_digit(a, R, T, nc, d) : (uint32_t)'0';
+        v |= ch << (8 * k);
+      }
+      o[g] = v;
+    }
+  }
+}
+
+// offs[i] = base + lens[0] + .. + lens[i-1] for i <= n, base = *basep (the end of the piece before, still
+// on the device) or 0: one block walks the array in tiles (a separate launch between the conversion and the
+// pack; no cross-workgroup waiting anywhere)
+constexpr int kDecScanThreads = 1024, kDecScanItems = 4;
+__global__ void __launch_bounds__(kDecScanThreads) k_dec_scan(const uint32_t* __restrict__ lens, size_t n,
+                                                              const uint64_t* __restrict__ basep,
+                                                              uint64_t* __restrict__ offs) {
+  __shared__ uint64_t wsum[kDecScanThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  uint64_t carry = basep ? *basep : 0ull;
+  for (size_t t0 = 0; t0 < n; t0 += (size_t)kDecScanThreads * kDecScanItems) {
+    const size_t i0 = t0 + (size_t)tid * kDecScanItems;
+    uint32_t v[kDecScanItems];
+    uint64_t s = 0;
+#pragma unroll
+    for (int k = 0; k < kDecScanItems; ++k) {
+      v[k] = i0 + k < n ? lens[i0 + k] : 0u;
+      s += v[k];
+    }
+    uint64_t inc = s;  // inclusive scan over the wave
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t o = (uint64_t)__shfl_up((unsigned long long)inc, (unsigned)d, 64);
+      if (lane >= d) inc += o;
+    }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    uint64_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kDecScanThreads / 64; ++w) {
+      const uint64_t x = wsum[w];
+      if (w < wave) before += x;
+      total += x;
+    }
+    uint64_t ex = carry + before + inc - s;
+#pragma unroll
+    for (int k = 0; k < kDecScanItems; ++k) {
+      if (i0 + k < n) offs[i0 + k] = ex;
+      ex += v[k];
+    }
+    carry += total;
+    __syncthreads();  // wsum is rewritten by the next tile
+  }
+  if (tid == 0) offs[n] = carry;
+}
+
+// one wave per row: the row's digits (right-aligned in its pitch) -> out + (offs[row] - offs[0]), bytes of
+// a row stored by consecutive lanes
+__global__ void __launch_bounds__(256) k_dec_pack(const uint8_t* __restrict__ dig, uint32_t pitch,
+                                                  const uint32_t* __restrict__ lens, const uint64_t* __restrict__ offs,
+                                                  size_t count, uint8_t* __restrict__ out) {
+  const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= count) return;
+  const uint32_t len = lens[row];
+  const uint8_t* src = dig + row * (size_t)pitch + (pitch - len);
+  uint8_t* dst = out + (offs[row] - offs[0]);
+  for (uint32_t t = threadIdx.x & 63; t < len; t += 64) dst[t] = src[t];
+}
+
+size_t dec_print_rows(int T) {
+  const size_t r = ((size_t)64 << 10) / 4 / ((size_t)T + 2);
+  return r < 64 ? r : 64;
+}
+
+hipError_t launch_dec_print(const uint32_t* X, size_t stride, size_t count, int S, int W, const uint32_t* nmod,
+                            size_t bits, uint32_t pitch, uint8_t* dig, uint32_t* lens, uint32_t* flags,
+                            hipStream_t st) {
+  if (count == 0) return hipSuccess;
+  const int T = dec10::row_words(bits, S);
+  const size_t R = dec_print_rows(T);
+  if (R == 0 || pitch % 4 != 0 || W < 24 || W > 31) return hipErrorInvalidValue;
+  const size_t lds = ((size_t)T + 2) * R * 4;
+  hipLaunchKernelGGL(k_dec_print, dim3((unsigned)((count + R - 1) / R)), dim3(64), lds, st, X, stride, count, S, W, nmod,
+                     (int)((bits + 31) / 32), T, (int)R, pitch, reinterpret_cast<uint32_t*>(dig), lens, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_dec_offsets(const uint32_t* lens, size_t count, const uint64_t* base, uint64_t* offs,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(k_dec_scan, dim3(1), dim3(kDecScanThreads), 0, st, lens, count, base, offs);
+  return hipGetLastError();
+}
+
+hipError_t launch_dec_pack(const uint8_t* dig, uint32_t pitch, const uint32_t* lens, const uint64_t* offs,
+                           size_t count, uint8_t* out, hipStream_t st) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_dec_pack, dim3((unsigned)((count + 3) / 4)), dim3(256), 0, st, dig, pitch, lens, offs, count,
+                     out);
+  return hipGetLastError();
 }
 
 hipError_t launch_dec_parse(int S, const uint32_t* chars4, const uint64_t* offs, uint64_t obase, size_t count,

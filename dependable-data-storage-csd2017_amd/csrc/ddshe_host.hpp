@@ -113,6 +113,9 @@ struct Worker {
   HostBuf hscan;   // coherent + mapped: string-table scans' match count, needle bytes and row ids
   HostBuf hbig;    // large read-backs (Search ids / match masks, Order permutations) before the caller's copy
   DevBuf dch[2], doff[2], rflags;
+  // decimal egress (rows_to_dec): fixed-pitch digits, packed chars, row lengths and offsets of the two
+  // pieces in flight (one being copied out while the next is converted)
+  DevBuf edig[2], echars[2], elens[2], eoffs[2];
   hipEvent_t ev_dec[2] = {};
   // decimal ingest: H2D copies on their own stream (chunk s + 1 copies while chunk s parses)
   hipStream_t cstream = nullptr;
@@ -591,6 +594,18 @@ int emit_be(const bn::Limbs& v, size_t width, uint8_t* out, size_t out_cap, size
 // the last kernel and before the first device-to-host copy.
 int rows_to_be(Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride, size_t count,
                bool reduce, uint8_t* out, size_t width, hipEvent_t before_copy = nullptr);
+// decimal digits of N - 1: no canonical residue's text is longer
+size_t dec_width(const ModConsts& mc);
+// The decimal counterpart of rows_to_be, and the one decimal egress path: rows of an rW column (any shape of
+// kShapes; reduce as above) -> BigInteger.toString text of their canonical residues, packed back to back in
+// `chars` with offsets[count + 1] (offsets[0] = 0), the layout ingest_dec takes. *chars_len = bytes
+// written; if they exceed chars_cap: DDS_E_BUFSIZE with *chars_len = bytes required (chars and offsets
+// unspecified). All on the GPU (k_dec_print, k_dec_scan, k_dec_pack) in pieces of bounded device staging
+// (DDSHE_DEC_PIECE_ROWS=<n> forces a piece size), one copy out of chars and one of offsets per piece, on
+// the worker's copy stream while the next piece's kernels run. Synchronises the stream. With ctx's timing
+// on, the pieces run one after the other and the kernels' device time goes to total_ms.
+int rows_to_dec(dds_ctx* ctx, Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride,
+                size_t count, bool reduce, char* chars, size_t chars_cap, uint64_t* offsets, size_t* chars_len);
 // Upload `count` big-endian operands into an rW column (X, stride) validated against mc; rows >= 2N
 // are reduced on the GPU and, when `reduced` is given, listed there (ascending).
 int ingest(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint8_t* ops, size_t width, size_t count,

@@ -265,5 +265,18 @@ hipError_t launch_dec_parse(int S, const uint32_t* chars4, const uint64_t* offs,
                             size_t stride, uint8_t* rowflags, uint32_t* flags, hipStream_t st);
 hipError_t launch_dec_fix(int S, uint32_t* X, size_t stride, size_t count, const uint8_t* rowflags,
                           const uint32_t* consts, uint32_t n0, hipStream_t st);
+// decimal egress: rows [0, count) of an rW matrix (any shape; values < 2·nmod when nmod != nullptr, else
+// canonical, below 2^bits either way after the reduction) -> their minimal decimal digits right-aligned in
+// `pitch` bytes per row (pitch a multiple of 4, dig 4-byte aligned) and lens[row]; flags[0] |= 1 for a row
+// whose text does not fit the pitch. Then offs[i] = base + sum of lens[0..i) for i <= count (base: a device
+// word, nullptr for 0), and the rows packed back to back at out + (offs[i] - offs[0]).
+hipError_t launch_dec_print(const uint32_t* X, size_t stride, size_t count, int S, int W, const uint32_t* nmod,
+                            size_t bits, uint32_t pitch, uint8_t* dig, uint32_t* lens, uint32_t* flags,
+                            hipStream_t st);
+size_t dec_print_rows(int T);  // rows per block of k_dec_print for dec10::row_words(bits, S) = T
+hipError_t launch_dec_offsets(const uint32_t* lens, size_t count, const uint64_t* base, uint64_t* offs,
+                              hipStream_t st);
+hipError_t launch_dec_pack(const uint8_t* dig, uint32_t pitch, const uint32_t* lens, const uint64_t* offs,
+                           size_t count, uint8_t* out, hipStream_t st);
 
 }  // namespace ddshe

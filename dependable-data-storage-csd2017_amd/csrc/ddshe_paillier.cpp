@@ -414,6 +414,86 @@ int col_fill_paillier_synth(dds_col* col, const uint8_t* n_be, size_t n_bytes, c
 }  // namespace host
 }  // namespace ddshe
 
+namespace {
+
+// what a batch encryption does with its ciphertext rows (an rW column over n^2, canonical): the binary
+// entry points hand them to rows_to_be, the decimal one to rows_to_dec
+using Egress = std::function<int(Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride)>;
+
+// HomoAdd.encrypt for a batch with the public key (count > 0, arguments checked by the caller).
+// nsq_bytes (nullable): the row width of a binary caller, checked against n^2 before anything else
+int encrypt_batch_pub(dds_ctx* ctx, const uint8_t* n_be, size_t n_bytes, const uint8_t* g_be, size_t g_bytes,
+                      const uint32_t* m, const uint8_t* r_be, size_t r_width, size_t count, const size_t* nsq_bytes,
+                      const Egress& egress) {
+  bn::Limbs n = bn::from_be(n_be, n_bytes);
+  bn::Limbs nsq = bn::mul(n, n);
+  if (nsq_bytes && *nsq_bytes < bn::byte_length(nsq)) return fail(DDS_E_BUFSIZE, "nsq_bytes too small");
+  std::vector<uint8_t> nsq_be(bn::byte_length(nsq));
+  bn::to_be(nsq, nsq_be.data(), nsq_be.size());
+  std::shared_ptr<ModConsts> mc;
+  int rc = get_mod(ctx, nsq_be.data(), nsq_be.size(), &mc);
+  if (rc) return rc;
+  bn::Limbs g = bn::from_be(g_be, g_bytes);
+  if ((rc = check_rows(*mc, count))) return rc;
+  WorkerLease wl(ctx);
+  if ((rc = wl.acquire())) return rc;
+  Worker* w = wl.w;
+  const int S = mc->S;
+  const size_t stride = round_up(count, 64);
+  HIP_TRY(w->x.ensure((size_t)S * stride * 4));
+  HIP_TRY(w->x2.ensure((size_t)S * stride * 4));
+  HIP_TRY(w->misc.ensure(count * 4));
+  if ((rc = ingest(ctx, w, wl.st, *mc, r_be, r_width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
+  HIP_TRY(hipMemcpyAsync(w->misc.p, m, count * 4, hipMemcpyHostToDevice, wl.st));
+  if ((rc = encrypt_device(w, wl.st, *mc, n, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
+                           w->x2.as<uint32_t>(), stride, true)))
+    return rc;
+  // w->misc held m until the ladder ran; encrypt_device has synchronised the stream, so the egress may
+  // re-ensure it as its staging
+  return egress(w, wl.st, *mc, w->x2.as<uint32_t>(), stride);
+}
+
+// The same with the private factors (dds_paillier_encrypt_batch_crt). n_check (nullable): the modulus the
+// caller passed beside p and q, which must be their product
+int encrypt_batch_crt(dds_ctx* ctx, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be, size_t q_bytes,
+                      const uint8_t* g_be, size_t g_bytes, const uint32_t* m, const uint8_t* r_be, size_t r_width,
+                      size_t count, const size_t* nsq_bytes, const bn::Limbs* n_check, const Egress& egress) {
+  std::shared_ptr<CrtKey> k;
+  int rc = get_crt_key(ctx, bn::from_be(p_be, p_bytes), bn::from_be(q_be, q_bytes), &k);
+  if (rc) return rc;
+  ModConsts& mn = *k->mn;
+  if (n_check && bn::cmp(*n_check, k->n) != 0) return fail(DDS_E_ARG, "n is not p * q");
+  if (nsq_bytes && *nsq_bytes < mn.bytes) return fail(DDS_E_BUFSIZE, "nsq_bytes too small");
+  for (size_t i = 0; i < count; ++i) {  // r in [1, n): the CRT halves need r < 2^bits(n)
+    bn::Limbs r = bn::from_be(r_be + i * r_width, r_width);
+    if (r.empty() || bn::cmp(r, k->n) >= 0) return fail(DDS_E_RANGE, "r must be in [1, n)");
+  }
+  const bn::Limbs g = bn::from_be(g_be, g_bytes);
+  if ((rc = check_rows(mn, count))) return rc;
+  WorkerLease wl(ctx);
+  if ((rc = wl.acquire())) return rc;
+  Worker* w = wl.w;
+  const int S = mn.S;
+  const size_t stride = round_up(count, 64);
+  HIP_TRY(w->x.ensure((size_t)S * stride * 4));
+  HIP_TRY(w->x2.ensure((size_t)S * stride * 4));
+  HIP_TRY(w->misc.ensure(count * 4));
+  if ((rc = ingest(ctx, w, wl.st, mn, r_be, r_width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
+  HIP_TRY(hipMemcpyAsync(w->misc.p, m, count * 4, hipMemcpyHostToDevice, wl.st));
+  if (crt_fits(*k))
+    rc = encrypt_crt_device(w, wl.st, *k, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
+                            w->x2.as<uint32_t>(), stride);
+  else  // unbalanced factors: public-key path (same result)
+    rc = encrypt_device(w, wl.st, mn, k->n, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
+                        w->x2.as<uint32_t>(), stride, true);
+  if (rc) return rc;
+  // w->misc held m until the ladders ran; both encrypt paths have synchronised the stream, so the egress
+  // may re-ensure it as its staging
+  return egress(w, wl.st, mn, w->x2.as<uint32_t>(), stride);
+}
+
+}  // namespace
+
 extern "C" {
 
 int dds_paillier_encrypt_batch(dds_ctx* ctx, const uint8_t* n_be, size_t n_bytes, const uint8_t* g_be, size_t g_bytes,
@@ -422,32 +502,33 @@ int dds_paillier_encrypt_batch(dds_ctx* ctx, const uint8_t* n_be, size_t n_bytes
   try {
     if (!ctx || !n_be || !g_be || r_width == 0 || (count && (!m || !r_be || !out))) return fail(DDS_E_ARG, "bad args");
     if (count == 0) return DDS_OK;
-    bn::Limbs n = bn::from_be(n_be, n_bytes);
-    bn::Limbs nsq = bn::mul(n, n);
-    if (nsq_bytes < bn::byte_length(nsq)) return fail(DDS_E_BUFSIZE, "nsq_bytes too small");
-    std::vector<uint8_t> nsq_be(bn::byte_length(nsq));
-    bn::to_be(nsq, nsq_be.data(), nsq_be.size());
-    std::shared_ptr<ModConsts> mc;
-    int rc = get_mod(ctx, nsq_be.data(), nsq_be.size(), &mc);
-    if (rc) return rc;
-    bn::Limbs g = bn::from_be(g_be, g_bytes);
-    if ((rc = check_rows(*mc, count))) return rc;
-    WorkerLease wl(ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    const int S = mc->S;
-    const size_t stride = round_up(count, 64);
-    HIP_TRY(w->x.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->x2.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->misc.ensure(count * 4));
-    if ((rc = ingest(ctx, w, wl.st, *mc, r_be, r_width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
-    HIP_TRY(hipMemcpyAsync(w->misc.p, m, count * 4, hipMemcpyHostToDevice, wl.st));
-    if ((rc = encrypt_device(w, wl.st, *mc, n, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
-                             w->x2.as<uint32_t>(), stride, true)))
-      return rc;
-    // w->misc held m until the ladder ran; encrypt_device has synchronised the stream, so rows_to_be may
-    // re-ensure it as its staging
-    return rows_to_be(w, wl.st, *mc, w->x2.as<uint32_t>(), stride, count, false, out, nsq_bytes);
+    return encrypt_batch_pub(ctx, n_be, n_bytes, g_be, g_bytes, m, r_be, r_width, count, &nsq_bytes,
+                             [&](Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride) {
+                               return rows_to_be(w, st, mc, X, stride, count, false, out, nsq_bytes);
+                             });
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_paillier_encrypt_batch_dec(dds_ctx* ctx, const uint8_t* n_be, size_t n_bytes, const uint8_t* g_be,
+                                   size_t g_bytes, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be,
+                                   size_t q_bytes, const uint32_t* m, const uint8_t* r_be, size_t r_width, size_t count,
+                                   char* chars, size_t chars_cap, uint64_t* offsets, size_t* chars_len) {
+  try {
+    if (!ctx || !n_be || !g_be || (!p_be) != (!q_be) || r_width == 0 || !offsets || !chars_len ||
+        (count && (!m || !r_be || !chars)))
+      return fail(DDS_E_ARG, "bad args");
+    *chars_len = 0;
+    offsets[0] = 0;
+    if (count == 0) return DDS_OK;
+    const Egress to_dec = [&](Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride) {
+      return rows_to_dec(ctx, w, st, mc, X, stride, count, false, chars, chars_cap, offsets, chars_len);
+    };
+    if (!p_be) return encrypt_batch_pub(ctx, n_be, n_bytes, g_be, g_bytes, m, r_be, r_width, count, nullptr, to_dec);
+    const bn::Limbs n = bn::from_be(n_be, n_bytes);
+    return encrypt_batch_crt(ctx, p_be, p_bytes, q_be, q_bytes, g_be, g_bytes, m, r_be, r_width, count, nullptr, &n,
+                             to_dec);
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");
   }
@@ -492,37 +573,11 @@ int dds_paillier_encrypt_batch_crt(dds_ctx* ctx, const uint8_t* p_be, size_t p_b
     if (!ctx || !p_be || !q_be || !g_be || r_width == 0 || (count && (!m || !r_be || !out)))
       return fail(DDS_E_ARG, "bad args");
     if (count == 0) return DDS_OK;
-    std::shared_ptr<CrtKey> k;
-    int rc = get_crt_key(ctx, bn::from_be(p_be, p_bytes), bn::from_be(q_be, q_bytes), &k);
-    if (rc) return rc;
-    ModConsts& mn = *k->mn;
-    if (nsq_bytes < mn.bytes) return fail(DDS_E_BUFSIZE, "nsq_bytes too small");
-    for (size_t i = 0; i < count; ++i) {  // r in [1, n): the CRT halves need r < 2^bits(n)
-      bn::Limbs r = bn::from_be(r_be + i * r_width, r_width);
-      if (r.empty() || bn::cmp(r, k->n) >= 0) return fail(DDS_E_RANGE, "r must be in [1, n)");
-    }
-    const bn::Limbs g = bn::from_be(g_be, g_bytes);
-    if ((rc = check_rows(mn, count))) return rc;
-    WorkerLease wl(ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    const int S = mn.S;
-    const size_t stride = round_up(count, 64);
-    HIP_TRY(w->x.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->x2.ensure((size_t)S * stride * 4));
-    HIP_TRY(w->misc.ensure(count * 4));
-    if ((rc = ingest(ctx, w, wl.st, mn, r_be, r_width, count, w->in, w->x.as<uint32_t>(), stride))) return rc;
-    HIP_TRY(hipMemcpyAsync(w->misc.p, m, count * 4, hipMemcpyHostToDevice, wl.st));
-    if (crt_fits(*k))
-      rc = encrypt_crt_device(w, wl.st, *k, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
-                              w->x2.as<uint32_t>(), stride);
-    else  // unbalanced factors: public-key path (same result)
-      rc = encrypt_device(w, wl.st, mn, k->n, g, w->misc.as<uint32_t>(), w->x.as<uint32_t>(), stride, count,
-                          w->x2.as<uint32_t>(), stride, true);
-    if (rc) return rc;
-    // w->misc held m until the ladders ran; both encrypt paths have synchronised the stream, so rows_to_be
-    // may re-ensure it as its staging
-    return rows_to_be(w, wl.st, mn, w->x2.as<uint32_t>(), stride, count, false, out, nsq_bytes);
+    return encrypt_batch_crt(ctx, p_be, p_bytes, q_be, q_bytes, g_be, g_bytes, m, r_be, r_width, count, &nsq_bytes,
+                             nullptr,
+                             [&](Worker* w, hipStream_t st, const ModConsts& mc, const uint32_t* X, size_t stride) {
+                               return rows_to_be(w, st, mc, X, stride, count, false, out, nsq_bytes);
+                             });
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");
   }

@@ -64,6 +64,7 @@ EXPORTS = [
     "dds_strtab_append", "dds_strtab_write_rows", "dds_strtab_set_live", "dds_strtab_rows", "dds_strtab_live_count",
     "dds_strtab_stats", "dds_strtab_truncate", "dds_host_register", "dds_host_unregister", "dds_host_alloc",
     "dds_host_free", "dds_paillier_decrypt_batch_crt", "dds_col_decrypt_paillier",
+    "dds_col_dec_width", "dds_col_read_dec", "dds_paillier_encrypt_batch_dec",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -100,6 +101,10 @@ _sig("dds_col_append_dec", C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64
 _sig("dds_col_count", _sz, C.c_void_p)
 _sig("dds_col_truncate", C.c_int, C.c_void_p, _sz)
 _sig("dds_col_read", C.c_int, C.c_void_p, _sz, _sz, _u8p)
+_sig("dds_col_dec_width", _sz, C.c_void_p)
+_sig("dds_col_read_dec", C.c_int, C.c_void_p, _sz, _sz, C.c_void_p, _sz, C.POINTER(C.c_uint64), _szp)
+_sig("dds_paillier_encrypt_batch_dec", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz,
+     C.c_char_p, _sz, C.POINTER(C.c_uint32), C.c_char_p, _sz, _sz, C.c_void_p, _sz, C.POINTER(C.c_uint64), _szp)
 _sig("dds_col_fold", C.c_int, C.c_void_p, _sz, _sz, _u8p, _sz, _szp)
 _sig("dds_col_fold_partial", C.c_int, C.c_void_p, _sz, _sz, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64))
 _sig("dds_col_partial_words", _sz, C.c_void_p)
@@ -222,6 +227,13 @@ def ints_to_be(xs, width: int) -> bytes:
 
 def nbytes(x: int) -> int:
     return max(1, (int(x).bit_length() + 7) // 8)
+
+
+def _split_dec(chars: np.ndarray, offs: np.ndarray) -> list[str]:
+    """The rows of an Arrow-style decimal column (uint8 chars, uint64 offsets[count+1]) as str."""
+    raw = chars.tobytes().decode("ascii")
+    o = offs.tolist()
+    return [raw[o[i]:o[i + 1]] for i in range(len(o) - 1)]
 
 
 def _ids(row_ids) -> np.ndarray:
@@ -486,6 +498,23 @@ class Engine:
         raw = bytes(out)
         return [int.from_bytes(raw[i * nb:(i + 1) * nb], "big") for i in range(len(rs))]
 
+    def paillier_encrypt_batch_dec(self, n: int, g: int, ms, rs, p: int | None = None, q: int | None = None) -> list[str]:
+        """dds_paillier_encrypt_batch_dec: the ciphertexts of paillier_encrypt_batch (or, with p and q,
+        of paillier_encrypt_batch_crt) as the BigInteger.toString text a PutSet carries, printed on the GPU."""
+        ms = np.ascontiguousarray(ms, dtype=np.uint32)
+        rs = [int(r) for r in rs]
+        count, rw = len(rs), max([1] + [nbytes(r) for r in rs])
+        pb = None if p is None else int_to_be(p, nbytes(p))
+        qb = None if q is None else int_to_be(q, nbytes(q))
+        chars = np.empty(max(1, count * len(str(n * n - 1))), dtype=np.uint8)
+        offs = np.zeros(count + 1, dtype=np.uint64)
+        used = C.c_size_t()
+        _check(_lib.dds_paillier_encrypt_batch_dec(
+            self._h, int_to_be(n, nbytes(n)), nbytes(n), int_to_be(g, nbytes(g)), nbytes(g), pb, len(pb or b""), qb,
+            len(qb or b""), ms.ctypes.data_as(C.POINTER(C.c_uint32)), ints_to_be(rs, rw), rw, count,
+            chars.ctypes.data, chars.nbytes, offs.ctypes.data_as(_u64p), C.byref(used)), "dds_paillier_encrypt_batch_dec")
+        return _split_dec(chars[:used.value], offs)
+
     def paillier_decrypt_batch_crt(self, p: int, q: int, g: int, cs) -> list[int]:
         """HomoAdd.decrypt(c, PaillierKey) for each c in cs (values in [0, n^2), coprime to n)."""
         cs = [int(c) for c in cs]
@@ -603,6 +632,9 @@ class Column(_Mutable):
             chars, offs = rows
             offs = np.ascontiguousarray(offs, dtype=np.uint64)
             n = len(offs) - 1
+            if isinstance(chars, np.ndarray):  # read_dec_buffer's chars: passed by address, no copy
+                keep = np.ascontiguousarray(chars, dtype=np.uint8)
+                chars = C.cast(C.c_void_p(keep.ctypes.data), C.c_char_p)
         else:
             enc = [r.encode() if isinstance(r, str) else bytes(r) for r in rows]
             chars = b"".join(enc)
@@ -623,6 +655,24 @@ class Column(_Mutable):
         out = np.empty((max(1, count), self.mb), dtype=np.uint8)
         _check(_lib.dds_col_read(self._h, first, count, out.ctypes.data_as(_u8p)), "dds_col_read")
         return out[:count]
+
+    @property
+    def dec_width(self) -> int:
+        """dds_col_dec_width: decimal digits of modulus - 1 (no row's text is longer)."""
+        return _lib.dds_col_dec_width(self._h)
+
+    def read_dec_buffer(self, first: int, count: int):
+        """dds_col_read_dec: rows [first, first+count) as BigInteger.toString text of their canonical
+        residues, printed on the GPU: (uint8 chars, uint64 offsets[count+1]), the layout append_dec takes."""
+        chars = np.empty(max(1, count * self.dec_width), dtype=np.uint8)
+        offs = np.zeros(count + 1, dtype=np.uint64)
+        used = C.c_size_t()
+        _check(_lib.dds_col_read_dec(self._h, first, count, chars.ctypes.data, chars.nbytes,
+                                     offs.ctypes.data_as(_u64p), C.byref(used)), "dds_col_read_dec")
+        return chars[:used.value], offs
+
+    def read_dec(self, first: int, count: int) -> list[str]:
+        return _split_dec(*self.read_dec_buffer(first, count))
 
     def fold(self, first: int = 0, count: int | None = None) -> int:
         count = len(self) - first if count is None else count

@@ -201,6 +201,18 @@ int dds_col_set_live(dds_col* col, const uint64_t* row_ids, size_t n, const uint
 size_t dds_col_live_count(dds_col* col);
 /* download rows [first, first+count) as canonical residues (x mod N), big-endian, mod_bytes each */
 int dds_col_read(dds_col* col, size_t first, size_t count, uint8_t* out);
+/* ---- decimal egress: rows out as the text the store holds ----
+ * DDSSet contents are BigInteger.toString text (DDSSet.scala:3, DDSJsonProtocol.scala:14-29), which is
+ * what a client PUTs after encrypting (SJHomoLibProvider.scala:58). The conversion runs on the GPU and
+ * returns the Arrow-style layout dds_col_append_dec takes.
+ * decimal digits of N-1: no row's text is longer */
+size_t dds_col_dec_width(const dds_col* col);
+/* rows [first, first+count), positional like dds_col_read (live bytes ignored, canonical residues):
+ * chars (no NULs, no separators) + offsets[count+1]; *chars_len = bytes written.
+ * chars_cap too small: DDS_E_BUFSIZE with *chars_len = bytes required; chars and offsets are unspecified then.
+ * count == 0: DDS_OK, offsets[0] = 0. Takes the column's lock shared, like the other reads. */
+int dds_col_read_dec(dds_col* col, size_t first, size_t count, char* chars, size_t chars_cap, uint64_t* offsets,
+                     size_t* chars_len);
 /* fold rows [first, first+count) (SumAll/MultAll semantics as dds_modmul_fold). A one-row fold returns
  * that row's operand as appended, unreduced (DDSRestServer.scala:416-417: the column remembers the
  * operands it had to store as residues); *out_len = max(modulus bytes, operand bytes). A negative
@@ -404,6 +416,16 @@ int dds_paillier_encrypt_batch(dds_ctx* ctx, const uint8_t* n_be, size_t n_bytes
 int dds_paillier_encrypt_batch_crt(dds_ctx* ctx, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be,
                                    size_t q_bytes, const uint8_t* g_be, size_t g_bytes, const uint32_t* m,
                                    const uint8_t* r_be, size_t r_width, size_t count, uint8_t* out, size_t nsq_bytes);
+
+/* HomoAdd.encrypt for a batch with the store's text as output (the client encrypts, SJHomoLibProvider.scala:58,
+ * and PUTs BigInteger.toString text, DDSSet.scala:3, DDSJsonProtocol.scala:14-29): same ciphertexts as
+ * dds_paillier_encrypt_batch (p_be == q_be == NULL) / _crt (both given, n = p*q; one without the other:
+ * DDS_E_ARG), printed on the GPU. chars + offsets[count+1] and the buffer-size rule as dds_col_read_dec. */
+int dds_paillier_encrypt_batch_dec(dds_ctx* ctx, const uint8_t* n_be, size_t n_bytes, const uint8_t* g_be,
+                                   size_t g_bytes, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be,
+                                   size_t q_bytes, const uint32_t* m, const uint8_t* r_be, size_t r_width,
+                                   size_t count, char* chars, size_t chars_cap, uint64_t* offsets,
+                                   size_t* chars_len);
 
 /* HomoAdd.decrypt(c, PaillierKey) (SJHomoLibProvider.scala:68) for `count` ciphertexts (big-endian,
  * `width` bytes each, values in [0, n^2): DDS_E_RANGE otherwise, and for a c not coprime to n).
