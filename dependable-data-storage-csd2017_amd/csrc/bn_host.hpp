@@ -418,6 +418,46 @@ inline uint32_t mont_n0(uint32_t n_low, int W) {
   return (0u - inv) & ((1u << W) - 1);
 }
 
+// floor(sqrt(a)) (Newton from above: x <- (x + a / x) / 2 until it stops decreasing)
+inline Limbs isqrt(const Limbs& a) {
+  if (a.empty()) return a;
+  Limbs x = pow2((bit_length(a) + 1) / 2);  // >= sqrt(a)
+  for (;;) {
+    Limbs q;
+    (void)mod(a, x, &q);
+    Limbs y = add(x, q);
+    (void)divmod_small(y, 2);
+    if (cmp(y, x) >= 0) return x;
+    x.swap(y);
+  }
+}
+
+// Constants of the base-n digit form of arithmetic mod N = n² (ddshe_foldsq.hpp), digits of s limbs of
+// W bits, R = 2^(W·s): k = -n⁻¹ mod 2^W; ñ = k·n ≡ -1 mod 2^W (the QP modulus of n); C = -k·(R - 1)
+// mod n; R mod n. sq_consts returns false unless N is an odd perfect square with
+// bits(n) <= W·s - W - 2 (then R > 4ñ and the digits, kept < 2ñ, fit s limbs).
+struct SqDigits {
+  uint32_t k = 0;
+  Limbs n, nq, C, Rmod;
+};
+inline bool sq_consts(const Limbs& N, int s, int W, SqDigits* out) {
+  if (N.empty() || (N[0] & 1u) == 0) return false;
+  // squares are 1 mod 8: rejects most moduli before the root is taken
+  if ((N[0] & 7u) != 1u) return false;
+  SqDigits d;
+  d.n = isqrt(N);
+  if (cmp(mul(d.n, d.n), N) != 0) return false;
+  if (bit_length(d.n) < 2 || bit_length(d.n) + (size_t)W + 2 > (size_t)W * s) return false;
+  d.k = mont_n0(d.n[0], W);
+  d.nq = mul(d.n, Limbs{d.k});
+  const Limbs R = pow2((size_t)W * s);
+  d.Rmod = mod(R, d.n);
+  const Limbs t = mod(mul(Limbs{d.k}, sub(R, Limbs{1})), d.n);  // k·(R - 1) mod n
+  d.C = t.empty() ? t : sub(d.n, t);
+  *out = d;
+  return true;
+}
+
 // ---- host modular product (the pairwise routes' lone requests) -----------------------------------
 // /Sum and /Mult (DDSRestServer.scala:385,479) are ONE modular product per request: a request with no
 // batch partner queued is served here rather than by a GPU round trip (ddshe_pairs.cpp). 64-bit limbs,

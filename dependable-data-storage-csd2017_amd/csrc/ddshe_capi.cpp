@@ -145,6 +145,26 @@ int get_mod(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, std::shared_p
     if (int rc = upload_qp(S, &mc->dqm)) return rc;
     mc->qbound = nq;  // level-1 partials are then < 2N~ too
   }
+  // N = n² in the (148, 4, 28) shape: constants of the digit form (the joined partials are < N + 2ñ < 2N,
+  // so qbound stands). A failed allocation only keeps the modulus on the opaque path.
+  if (S == kFoldSqWide && mc->S2 >= 2 * kFoldSqLimbs) {
+    bn::SqDigits sd;
+    if (bn::sq_consts(N, kFoldSqLimbs, mc->W, &sd)) {
+      std::vector<uint32_t> h;
+      for (const bn::Limbs* v : {&sd.nq, &sd.n, &sd.C, &sd.Rmod}) {  // kSqNq, kSqN, kSqC, kSqRmod
+        const std::vector<uint32_t> r = bn::to_rw(*v, kFoldSqLimbs, mc->W);
+        h.insert(h.end(), r.begin(), r.end());
+      }
+      if (hipMalloc(&mc->dsq, h.size() * 4) == hipSuccess) {
+        if (hipMemcpy(mc->dsq, h.data(), h.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+          return fail(DDS_E_HIP, "const upload");
+        mc->sq = std::make_unique<bn::SqDigits>(std::move(sd));
+      } else {
+        mc->dsq = nullptr;
+        (void)hipGetLastError();
+      }
+    }
+  }
   std::lock_guard<std::mutex> lk(ctx->mu);
   auto it = ctx->mods.find(key);
   if (it != ctx->mods.end()) {
@@ -256,11 +276,58 @@ size_t narrow_fold_rows() {
   return n;
 }
 
+FoldDigits col_fold_digits(dds_col* col, hipStream_t st, size_t first, size_t count, const uint32_t* d_ids) {
+  ModConsts& mc = *col->mc;
+  if (!mc.sq || d_ids || !fold_sq_enabled() || count < fold_sq_min_rows(col->ctx->cus)) return FoldDigits();
+  std::lock_guard<std::mutex> lk(col->sqmu);
+  if (col->digits_failed) return FoldDigits();
+  if (!col->digits && hipMalloc(&col->digits, (size_t)2 * kFoldSqLimbs * col->stride * 4) != hipSuccess) {
+    (void)hipGetLastError();
+    col->digits = nullptr;
+    col->digits_failed = true;
+    return FoldDigits();
+  }
+  const size_t end = first + count;
+  if (col->digits_rows < end) {
+    // the watermark is published only once the rows are converted: a concurrent fold reads the mirror
+    // on another stream
+    const size_t r0 = col->digits_rows;
+    if (launch_to_digits(col->d + r0, col->stride, end - r0, mc.dsq, mc.sq->k, col->digits + r0, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return FoldDigits();
+    col->digits_rows = end;
+  }
+  return FoldDigits{col->digits + first, col->stride};
+}
+
 // Level 1 (throughput shape, G groups: group g holds prod_g * R^(1 - c_g)) over `count` rows of X (or
-// rows d_ids[0..count)), unless the fold is small enough for the tree alone.
+// rows d_ids[0..count)), unless the fold is small enough for the tree alone. dg.D: the rows' base-n
+// digits (col_fold_digits): level 1 runs in digit form (k_fold_sq) and k_sq_join hands the tail the same
+// leaves k_fold would, with another power of two.
 int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
-                size_t count, const uint32_t* d_ids, Leaves* lv, size_t max_groups) {
+                size_t count, const uint32_t* d_ids, Leaves* lv, size_t max_groups, const FoldDigits& dg) {
   const int S = mc.S, S2 = mc.S2;
+  if (dg.D && !d_ids && mc.sq && count >= 2) {
+    size_t gmax = fold_sq_max_groups(ctx->cus);
+    if (max_groups) gmax = std::min(gmax, max_groups);
+    const size_t G = std::min(gmax, std::max<size_t>(1, count / 2)), ps = round_up(G, 64);
+    HIP_TRY(w->p0.ensure((size_t)S2 * ps * 4));
+    HIP_TRY(w->sqp.ensure((size_t)2 * kFoldSqLimbs * ps * 4));
+    record_time(ctx, w, st, true, 0);
+    HIP_TRY(launch_fold_sq(dg.D, dg.stride, count, mc.dsq, mc.sq->k, w->sqp.as<uint32_t>(), ps, G, st));
+    record_time(ctx, w, st, false, 0);
+    if (ctx->timing.load()) {
+      w->timed_fold = true;
+      std::lock_guard<std::mutex> lk(ctx->tmu);
+      ctx->pending_modmuls = count - G;
+    }
+    HIP_TRY(launch_sq_join(w->sqp.as<uint32_t>(), ps, G, mc.dsq, mc.sq->k, w->p0.as<uint32_t>(), ps, S2, st));
+    // a row's digits hold X·R⁻¹ and each of the count - G products adds one R⁻¹ (R = 2^(W·76)); the join
+    // is exact
+    *lv = Leaves{w->p0.as<uint32_t>(), ps, S2, mc.W, G,
+                 -(int64_t)mc.W * kFoldSqLimbs * (2 * (int64_t)count - (int64_t)G), nullptr};
+    return DDS_OK;
+  }
   if (use_tree() && mc.tree_direct && count <= tree_direct_rows()) {
     *lv = Leaves{X, xstride, S, mc.W, count, 0, d_ids};
     return DDS_OK;
@@ -480,7 +547,8 @@ int reduce_leaves(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const 
 }
 
 int fold_partial_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
-                        size_t count, const uint32_t** part, size_t* part_stride, int64_t* E, const uint32_t* d_ids) {
+                        size_t count, const uint32_t** part, size_t* part_stride, int64_t* E, const uint32_t* d_ids,
+                        const FoldDigits& dg) {
   // DDSHE_PARTIAL_GROUPS (A/B of the strong-split share): cap level 1's groups so the
   // share's partials go straight to the tree (<= 4096) instead of through the tail launches
   static const size_t cap = [] {
@@ -488,16 +556,16 @@ int fold_partial_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, 
     return e ? (size_t)atoll(e) : (size_t)0;
   }();
   Leaves lv;
-  int rc = fold_level1(ctx, w, st, mc, X, xstride, count, d_ids, &lv, cap);
+  int rc = fold_level1(ctx, w, st, mc, X, xstride, count, d_ids, &lv, cap, dg);
   if (rc) return rc;
   *part_stride = 1;
   return reduce_leaves(ctx, w, st, mc, lv, false, nullptr, part, E);
 }
 
 int fold_value_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
-                      size_t count, const uint32_t* d_ids, bn::Limbs* value) {
+                      size_t count, const uint32_t* d_ids, bn::Limbs* value, const FoldDigits& dg) {
   Leaves lv;
-  int rc = fold_level1(ctx, w, st, mc, X, xstride, count, d_ids, &lv);
+  int rc = fold_level1(ctx, w, st, mc, X, xstride, count, d_ids, &lv, 0, dg);
   if (rc) return rc;
   lv.rows = count;
   return reduce_leaves(ctx, w, st, mc, lv, true, value, nullptr, nullptr);
@@ -1200,7 +1268,8 @@ int col_fold_value(dds_col* col, const uint64_t* row_ids, size_t first, size_t n
     d_ids = w->ids.as<uint32_t>();
   }
   // synchronises: ids32 may go afterwards
-  return fold_value_device(col->ctx, w, wl.st, mc, X, col->stride, n, d_ids, v);
+  const FoldDigits dg = row_ids ? FoldDigits() : col_fold_digits(col, wl.st, first, n, d_ids);
+  return fold_value_device(col->ctx, w, wl.st, mc, X, col->stride, n, d_ids, v, dg);
 }
 
 int col_live_range(dds_col* col, Worker* w, hipStream_t st, size_t first, size_t count, const uint32_t** d_ids,
@@ -1216,7 +1285,8 @@ int col_live_range(dds_col* col, Worker* w, hipStream_t st, size_t first, size_t
   uint64_t total = 0;
   HIP_TRY(read_sync(w, st, w->flags.p, &total, 8));
   *n = (size_t)total;
-  *d_ids = w->ids.as<uint32_t>();
+  // every row of the range is live (the dead ones are elsewhere): the fold runs over the range itself
+  *d_ids = total == count ? nullptr : w->ids.as<uint32_t>();
   return DDS_OK;
 }
 
@@ -1740,7 +1810,8 @@ size_t dds_col_count(const dds_col* col) { return col ? col->count : 0; }
 
 int dds_col_truncate(dds_col* col, size_t count) {
   if (!col) return fail(DDS_E_ARG, "bad arguments");
-  std::unique_lock<std::shared_mutex> lk(col->mu);
+  ColWriteLock lk(col);
+  lk.touches_from(std::min(count, col->count));
   if (count > col->count) return fail(DDS_E_ARG, "truncate beyond the row count");
   if (col->ndead) {  // dropped rows come back live (rows past `count` always are)
     size_t dropped = 0;
@@ -1762,7 +1833,8 @@ int dds_col_truncate(dds_col* col, size_t count) {
 int dds_col_write_rows(dds_col* col, const uint64_t* row_ids, size_t n, const uint8_t* operands_be, size_t width) {
   try {
     if (!col || (n && (!row_ids || !operands_be || width == 0))) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
+    ColWriteLock lk(col);
+    lk.touches_from(n ? (size_t)*std::min_element(row_ids, row_ids + n) : ColWriteLock::kNoRow);
     RowWrite plan;
     int rc = col_write_prepare(col, row_ids, n, operands_be, width, nullptr, nullptr, &plan);
     return rc ? rc : col_write_commit(col, plan);
@@ -1775,7 +1847,8 @@ int dds_col_write_rows_dec(dds_col* col, const uint64_t* row_ids, size_t n, cons
                            const uint64_t* offsets) {
   try {
     if (!col || (n && (!row_ids || !chars || !offsets))) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
+    ColWriteLock lk(col);
+    lk.touches_from(n ? (size_t)*std::min_element(row_ids, row_ids + n) : ColWriteLock::kNoRow);
     RowWrite plan;
     int rc = col_write_prepare(col, row_ids, n, nullptr, 0, chars, offsets, &plan);
     return rc ? rc : col_write_commit(col, plan);
@@ -1787,7 +1860,8 @@ int dds_col_write_rows_dec(dds_col* col, const uint64_t* row_ids, size_t n, cons
 int dds_col_set_live(dds_col* col, const uint64_t* row_ids, size_t n, const uint8_t* live) {
   try {
     if (!col || (n && (!row_ids || !live))) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
+    ColWriteLock lk(col);
+    lk.touches_from(ColWriteLock::kNoRow);
     return col_set_live(col, row_ids, n, live);
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");
@@ -1800,12 +1874,20 @@ size_t dds_col_live_count(dds_col* col) {
   return col->count - col->ndead;
 }
 
+size_t dds_col_digit_rows(dds_col* col) {
+  if (!col) return 0;
+  std::shared_lock<std::shared_mutex> lk(col->mu);
+  std::lock_guard<std::mutex> ls(col->sqmu);
+  return col->digits ? col->digits_rows : 0;
+}
+
 size_t dds_col_partial_words(const dds_col* col) { return col ? partial_words_for(*col->mc) : 0; }
 
 int dds_col_append(dds_col* col, const uint8_t* ops, size_t width, size_t count) {
   try {
     if (!col || width == 0 || (count && !ops)) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
+    ColWriteLock lk(col);
+    lk.touches_from(col->count);  // an append
     if (col->count + count > col->capacity) return fail(DDS_E_ARG, "column capacity exceeded");
     if (count == 0) return DDS_OK;
     WorkerLease wl(col->ctx);
@@ -1828,7 +1910,8 @@ int dds_col_append(dds_col* col, const uint8_t* ops, size_t width, size_t count)
 int dds_col_append_dec(dds_col* col, const char* chars, const uint64_t* offsets, size_t count) {
   try {
     if (!col || (count && (!chars || !offsets))) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
+    ColWriteLock lk(col);
+    lk.touches_from(col->count);  // an append
     if (col->count + count > col->capacity) return fail(DDS_E_ARG, "column capacity exceeded");
     if (count == 0) return DDS_OK;
     for (size_t i = 0; i < count; ++i)
@@ -1925,7 +2008,7 @@ int dds_col_fold_partial(dds_col* col, size_t first, size_t count, uint32_t* par
       const uint32_t* part;
       size_t ps;
       if ((rc = fold_partial_device(col->ctx, wl.w, wl.st, mc, col->d + first, col->stride, count, &part, &ps, &E,
-                                    d_ids)))
+                                    d_ids, col_fold_digits(col, wl.st, first, count, d_ids))))
         return rc;
       HIP_TRY(hipMemcpy2DAsync(partial, 4, part, ps * 4, 4, S2, hipMemcpyDeviceToHost, wl.st));
       HIP_TRY(hipStreamSynchronize(wl.st));
@@ -2032,7 +2115,7 @@ int dds_col_fold_partial_device(dds_col* col, size_t first, size_t count, uint32
       const uint32_t* part;
       size_t ps;
       if ((rc = fold_partial_device(col->ctx, wl.w, wl.st, mc, col->d + first, col->stride, count, &part, &ps, &E,
-                                    d_ids)))
+                                    d_ids, col_fold_digits(col, wl.st, first, count, d_ids))))
         return rc;
       HIP_TRY(launch_strided_copy(part, 0, ps, d_partial, 0, 1, 1, S2, wl.st));
     }
@@ -2050,7 +2133,8 @@ int dds_col_fill_table_synth(dds_col* col, const uint8_t* table_be, size_t width
                              uint64_t row0, size_t count) {
   try {
     if (!col || !table_be || width == 0 || tcount == 0 || tcount > 0xFFFFFFFFu) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
+    ColWriteLock lk(col);
+    lk.touches_from(col->count);  // an append
     if (col->count + count > col->capacity) return fail(DDS_E_ARG, "column capacity exceeded");
     WorkerLease wl(col->ctx);
     int rc;
@@ -2073,7 +2157,8 @@ int dds_col_fill_table_synth(dds_col* col, const uint8_t* table_be, size_t width
 int dds_col_fill_random(dds_col* col, size_t bits, uint64_t seed, uint64_t row0, size_t count) {
   try {
     if (!col || bits == 0) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
+    ColWriteLock lk(col);
+    lk.touches_from(col->count);  // an append
     if (col->count + count > col->capacity) return fail(DDS_E_ARG, "column capacity exceeded");
     if (bits >= col->mc->bits) return fail(DDS_E_RANGE, "random rows must stay below the modulus");
     WorkerLease wl(col->ctx);

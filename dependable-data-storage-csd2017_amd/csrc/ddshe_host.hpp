@@ -92,6 +92,7 @@ struct Worker {
   DevBuf in, in2, x, x2, p0, p1, out, flags, y, misc, misc2, tab, ids;
   DevBuf pk, gather;         // multi-device fold: packed partial (shard side), gathered partials (combiner)
   DevBuf tree;               // reduction tree: node values + arrival flags
+  DevBuf sqp;                // digit-form fold: level-1 partials in digits, before the join
   hipEvent_t ev_peer = {};   // shard partial copied to the combining device
   // a device counter kept at zero between uses (the Search bitmask's match count: the count kernel's
   // tiles add into it, it is read, then re-zeroed on the stream after the read); ev_done marks the read
@@ -154,6 +155,10 @@ struct ModConsts {
   int S3 = 0, W3 = 0;            // reduction-tree shape (ddshe_tree.hip), R3 = 2^(W3*S3)
   bool tree_direct = false;      // raw rows (< 2^(W*S)) may be tree leaves: 2^(2WS) <= R3 * 2^(bits(N)-1)
   uint32_t* d3 = nullptr;        // tree constants: N | n' = -N^-1 mod R3 | N | 2N | 3N | R3^2 mod N
+  // N = n², an odd perfect square in the (148, 4, 28) shape: constants of the base-n digit form
+  // (ddshe_foldsq.hpp) and their device copy (kSqCount vectors of kFoldSqLimbs limbs), else null
+  std::unique_ptr<bn::SqDigits> sq;
+  uint32_t* dsq = nullptr;
   std::map<int64_t, std::vector<uint32_t>> y3cache;  // E -> 2^(W3*S3 - E) mod N, tree limbs
   std::mutex ymu;
   std::map<int64_t, std::vector<uint32_t>> ycache;  // E -> 2^(W*S2 - E) mod N, tail limbs
@@ -168,6 +173,7 @@ struct ModConsts {
     if (dq) (void)hipFree(dq);
     if (dqm) (void)hipFree(dqm);
     if (d3) (void)hipFree(d3);
+    if (dsq) (void)hipFree(dsq);
     if (y3slab) (void)hipFree(y3slab);
     if (dtab) (void)hipFree(dtab);
   }
@@ -309,8 +315,19 @@ struct dds_col {
     bool neg = false;
   };
   std::map<size_t, Orig> orig;
+  // Digit mirror of a column over n² (ModConsts::sq): rows [0, digits_rows) of `digits` hold the rows'
+  // two base-n digits (limb-major at the column's stride, 2 * kFoldSqLimbs limb rows: the n⁰-digit, then
+  // the n¹-digit; fully normalised), X ≡ R·(w + c·n). Allocated by the first fold that wants it (a failed
+  // allocation leaves the column on the opaque path for good) and kept current lazily: holders of mu
+  // (exclusive) lower digits_rows to the first row they may have changed (ColWriteLock), a fold converts
+  // the rows it needs past the watermark under sqmu (folds hold mu shared).
+  uint32_t* digits = nullptr;
+  size_t digits_rows = 0;
+  bool digits_failed = false;
+  std::mutex sqmu;
   ~dds_col() {
     if (d) (void)hipFree(d);
+    if (digits) (void)hipFree(digits);
     if (dlive) (void)hipFree(dlive);
   }
 };
@@ -318,6 +335,26 @@ struct dds_col {
 
 namespace ddshe {
 namespace host {
+
+// The column lock held exclusively by a mutation. When it ends, the digit mirror's watermark drops to
+// the first row the holder may have changed: row 0 unless the holder says otherwise (touches_from), so a
+// writer that says nothing costs a re-conversion, never a stale digit. This is the only place the
+// watermark is lowered.
+struct ColWriteLock {
+  static constexpr size_t kNoRow = ~(size_t)0;  // no stored row changed (liveness only)
+  dds_col* col;
+  std::unique_lock<std::shared_mutex> lk;
+  size_t first = 0;
+  explicit ColWriteLock(dds_col* c) : col(c), lk(c->mu) {}
+  ColWriteLock(dds_col* c, std::defer_lock_t) : col(c), lk(c->mu, std::defer_lock) {}
+  ColWriteLock(const ColWriteLock&) = delete;
+  ColWriteLock& operator=(const ColWriteLock&) = delete;
+  // rows below `row` keep their value (an append: the row count when the lock was taken)
+  void touches_from(size_t row) { first = row; }
+  ~ColWriteLock() {
+    if (lk.owns_lock()) col->digits_rows = std::min(col->digits_rows, first);
+  }
+};
 
 // Coalescing queue of the pairwise routes for one modulus: a caller queues its pair; whoever finds
 // a batch slot free becomes a leader and runs one k_pairs launch over everything queued so far (group
@@ -573,18 +610,29 @@ struct Leaves {
   size_t gs = 1;
   size_t rows = 0;  // rows folded into these leaves (finalize: how the host waits for the root)
 };
+// The digits of the rows a fold reads, when the fold may run in digit form: D (the mirror at the fold's
+// first row; null: the opaque path) and its stride
+struct FoldDigits {
+  const uint32_t* D = nullptr;
+  size_t stride = 0;
+};
+// Brings the mirror of `col` up to row first + count and returns it at row `first`; an empty FoldDigits
+// when the column, the fold size or DDSHE_FOLD_SQ rules the digit form out (never an error: the fold
+// then runs as before). Caller holds col->mu (shared or exclusive). May synchronise the stream.
+FoldDigits col_fold_digits(dds_col* col, hipStream_t st, size_t first, size_t count, const uint32_t* d_ids);
 int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
-                size_t count, const uint32_t* d_ids, Leaves* lv, size_t max_groups = 0);
+                size_t count, const uint32_t* d_ids, Leaves* lv, size_t max_groups = 0,
+                const FoldDigits& dg = FoldDigits());
 int reduce_leaves(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const Leaves& lv, bool finalize,
                   bn::Limbs* value, const uint32_t** part, int64_t* Eout);
 // canonical product of `count` rows (rows d_ids[0..count) when given); synchronises the stream
 int fold_value_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
-                      size_t count, const uint32_t* d_ids, bn::Limbs* value);
+                      size_t count, const uint32_t* d_ids, bn::Limbs* value, const FoldDigits& dg = FoldDigits());
 // Fold `count` rows of an rW column (rows ids[0..count) when d_ids != nullptr) into one un-finalised
 // partial: tail-shape limbs (row 0 of `*part`, stride `*part_stride`) holding prod(rows) * 2^(*E).
 int fold_partial_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
                         size_t count, const uint32_t** part, size_t* part_stride, int64_t* E,
-                        const uint32_t* d_ids = nullptr);
+                        const uint32_t* d_ids = nullptr, const FoldDigits& dg = FoldDigits());
 void account_fold(dds_ctx* ctx, Worker* w);
 int emit_be(const bn::Limbs& v, size_t width, uint8_t* out, size_t out_cap, size_t* out_len);
 // rows of an rW column (shape of mc) -> `width`-byte big-endian rows at `out` (host). reduce: rows are

@@ -48,6 +48,23 @@ hipError_t launch_fold(int S, const uint32_t* X, size_t xstride, size_t count, c
                        int lane1 = 0,  // != 0: one bignum per lane (k_fold1) at lane1 = fold1_limbs(S, bits) limbs
                        size_t inblock_pgs = 0);  // != 0: k_fold InBlock, one row-major leaf of this many words per block
 bool fold_qp_enabled();
+// Digit-form fold of a perfect-square modulus n² in the (148, 4, 28) shape (ddshe_foldsq.hpp): values as
+// two base-n digits of kFoldSqLimbs limbs each. sq: kSqCount vectors of kFoldSqLimbs limbs (ñ = k·n | n |
+// C | R mod n), k = -n⁻¹ mod 2^28. The mirror D and the digit partials Q are limb-major, 2·kFoldSqLimbs
+// limb rows (digit 0, then digit 1). DDSHE_FOLD_SQ=0 disables the path, DDSHE_FOLD_SQ_MIN=<rows>
+// overrides the row count from which a fold takes it.
+constexpr int kFoldSqLimbs = 76, kFoldSqWide = 148;
+enum { kSqNq = 0, kSqN = 1, kSqC = 2, kSqRmod = 3, kSqCount = 4 };
+bool fold_sq_enabled();
+size_t fold_sq_min_rows(int cus);
+size_t fold_sq_max_groups(int cus);
+hipError_t launch_to_digits(const uint32_t* X, size_t stride, size_t count, const uint32_t* sq, uint32_t k,
+                            uint32_t* D, hipStream_t st);
+hipError_t launch_fold_sq(const uint32_t* D, size_t stride, size_t count, const uint32_t* sq, uint32_t k, uint32_t* Q,
+                          size_t qstride, size_t ngroups, hipStream_t st);
+// digit partials -> X = w + (c mod n)·n < 2N in s_out (= 160) limbs, limb-major at pstride
+hipError_t launch_sq_join(const uint32_t* Q, size_t qstride, size_t ngroups, const uint32_t* sq, uint32_t k,
+                          uint32_t* P, size_t pstride, int s_out, hipStream_t st);
 // k_fold1 (one bignum per lane) exists for S (40, 76) and is worth its longer per-product latency for
 // folds of at least fold1_min_rows(S) rows (DDSHE_FOLD1=0 disables it, DDSHE_FOLD1_MIN=<rows> overrides)
 bool fold1_shape(int S);

@@ -153,7 +153,9 @@ int mcol_fold(dds_mcol* mcol, const uint64_t* ids, size_t n, bn::Limbs* v, bool*
     }
     const uint32_t* part;
     size_t ps;
-    if ((r = fold_partial_device(cs, l.w, l.st, *col->mc, col->d, col->stride, rows, &part, &ps, &Es[j], d_ids)))
+    // every shard is a dds_col with a digit mirror of its own (shard rows stay put: the shared locks above)
+    if ((r = fold_partial_device(cs, l.w, l.st, *col->mc, col->d, col->stride, rows, &part, &ps, &Es[j], d_ids,
+                                 col_fold_digits(col, l.st, 0, rows, d_ids))))
       return r;
     // pack the partial (S2 limbs at stride ps) into S2 consecutive words, then device-to-device
     HIP_TRY(l.w->pk.ensure(S2 * 4));
@@ -211,8 +213,12 @@ int mcol_write(dds_mcol* c, const uint64_t* ids, size_t n, const uint8_t* ops, s
   if (rc) return rc;
   DeviceGuard dg;
   const size_t G = c->cols.size();
-  std::vector<std::unique_lock<std::shared_mutex>> locks;
-  for (auto col : c->cols) locks.emplace_back(col->mu);
+  std::vector<std::unique_ptr<ColWriteLock>> locks;
+  for (size_t s = 0; s < G; ++s) {
+    locks.push_back(std::make_unique<ColWriteLock>(c->cols[s]));
+    locks[s]->touches_from(lids[s].empty() ? ColWriteLock::kNoRow
+                                           : (size_t)*std::min_element(lids[s].begin(), lids[s].end()));
+  }
   std::vector<RowWrite> plans(G);
   for (size_t s = 0; s < G; ++s) {
     if (lids[s].empty()) continue;
@@ -369,7 +375,8 @@ int dds_mcol_set_live(dds_mcol* c, const uint64_t* row_ids, size_t n, const uint
       if (lids[s].empty()) continue;
       std::vector<uint8_t> f(lids[s].size());
       for (size_t j = 0; j < f.size(); ++j) f[j] = live[pos[s][j]];
-      std::unique_lock<std::shared_mutex> lc(c->cols[s]->mu);
+      ColWriteLock lc(c->cols[s]);
+      lc.touches_from(ColWriteLock::kNoRow);
       if ((rc = col_set_live(c->cols[s], lids[s].data(), f.size(), f.data()))) return rc;
     }
     return DDS_OK;

@@ -351,7 +351,8 @@ int col_fill_paillier_synth(dds_col* col, const uint8_t* n_be, size_t n_bytes, c
                             uint32_t shard) {
   try {
     if (!col || !n_be || !g_be || pool_size == 0 || shards == 0 || shard >= shards) return fail(DDS_E_ARG, "bad arguments");
-    std::unique_lock<std::shared_mutex> lk(col->mu);
+    ColWriteLock lk(col);
+    lk.touches_from(col->count);  // an append
     if (col->count + count > col->capacity) return fail(DDS_E_ARG, "column capacity exceeded");
     ModConsts& mc = *col->mc;
     bn::Limbs n = bn::from_be(n_be, n_bytes), g = bn::from_be(g_be, g_bytes);
@@ -590,10 +591,11 @@ int dds_col_encrypt_paillier(dds_col* out, dds_col* rcol, size_t r_first, const 
     if (!out || !rcol || !n_be || !g_be || (count && !d_m) || (!p_be) != (!q_be)) return fail(DDS_E_ARG, "bad args");
     if (count == 0) return DDS_OK;
     if (r_first + count > rcol->count) return fail(DDS_E_ARG, "r rows out of range");
-    std::unique_lock<std::shared_mutex> lk(out->mu, std::defer_lock);
-    std::unique_lock<std::shared_mutex> lr(rcol->mu, std::defer_lock);
+    ColWriteLock lk(out, std::defer_lock);
+    std::unique_lock<std::shared_mutex> lr(rcol->mu, std::defer_lock);  // rcol is only read
     if (out == rcol) return fail(DDS_E_ARG, "out and r columns must differ");
-    std::lock(lk, lr);
+    std::lock(lk.lk, lr);
+    lk.touches_from(out->count);  // an append
     if (out->count + count > out->capacity) return fail(DDS_E_ARG, "column capacity exceeded");
     const bn::Limbs n = bn::from_be(n_be, n_bytes), g = bn::from_be(g_be, g_bytes);
     const bn::Limbs nsq = bn::mul(n, n);

@@ -199,6 +199,12 @@ int dds_col_write_rows_dec(dds_col* col, const uint64_t* row_ids, size_t n, cons
                            const uint64_t* offsets);
 int dds_col_set_live(dds_col* col, const uint64_t* row_ids, size_t n, const uint8_t* live);
 size_t dds_col_live_count(dds_col* col);
+/* Rows [0, n) of the column's base-n digit mirror that are current. A column over a perfect-square modulus
+ * n^2 (Paillier) of 3135..4142 bits keeps, from its first long fold on, a second copy of its rows as two
+ * base-n digits (608 bytes per row beside the 592 of the row itself), which those folds read instead;
+ * mutations lower n, the next fold converts what it needs. 0: no mirror (other moduli, short folds only,
+ * DDSHE_FOLD_SQ=0, or the allocation failed and the column folds as before). See INTEGRATION.md. */
+size_t dds_col_digit_rows(dds_col* col);
 /* download rows [first, first+count) as canonical residues (x mod N), big-endian, mod_bytes each */
 int dds_col_read(dds_col* col, size_t first, size_t count, uint8_t* out);
 /* ---- decimal egress: rows out as the text the store holds ----
