@@ -22,8 +22,9 @@ bool fold_sq_enabled() {
 
 // With few rows per group of a full grid the level-1 launch is latency-bound and the digit form only adds
 // the join launch; the mad count decides once the launch is throughput-bound. Measured on an MI355X
-// (committed key, resident rows, median wall time of dds_col_fold; profiles/foldsq_ab.txt): 0.338 against
-// 0.334 ms at 131,072 rows, 0.542 / 0.538 at 262,144, 0.85 / 0.94 at 524,288, 1.46 / 1.76 at 1,048,576.
+// (committed key, resident rows, median wall time of dds_col_fold, tools/fold_sq_sweep.py;
+// profiles/foldsq_chainb_ab.txt): 0.331 against 0.334 ms at 131,072 rows, 0.536 / 0.538 at 262,144 (ties:
+// under 1 % either way), 0.75 / 0.94 at 524,288, 1.25 / 1.66 at 1,048,576.
 // The default is the smallest measured count at which it wins: 16 rows per group of a full grid.
 size_t fold_sq_min_rows(int cus) {
   static const long long env = [] {

@@ -47,6 +47,10 @@ struct MontSq {
     t[L - 1] = (uint64_t)grp_from_next<TPI>(lo0);
   }
 
+  // Not dead code: without it LLVM reassociates chain B's dependent mads into (x0·y1 + 0, x1·y0 + tmp, tmp + tB),
+  // one extra 64-bit add per limb (tests/test_fold_sq_isa.py); the sums and their order stay as written.
+  __device__ __forceinline__ static void pin(uint64_t& t) { asm volatile("" : "+v"(t)); }
+
   // one fused step with the row's digit limbs y0, y1; kbot = k on the group's lane 0, 0 elsewhere
   __device__ __forceinline__ static void step(uint64_t (&tA)[L], uint64_t (&tB)[L], const uint32_t (&x0)[L],
                                               const uint32_t (&x1)[L], const uint32_t (&nq)[L], uint32_t y0,
@@ -55,7 +59,9 @@ struct MontSq {
     const uint32_t qa = (uint32_t)tA[0] & kMask;
     const uint32_t mA = grp_bcast0<TPI>(qa);
     tB[0] = (uint64_t)x0[0] * y1 + tB[0];
+    pin(tB[0]);
     tB[0] = (uint64_t)x1[0] * y0 + tB[0];
+    pin(tB[0]);
     tB[0] = (uint64_t)kbot * (kMask - qa) + tB[0];
     const uint32_t mB = grp_bcast0<TPI>((uint32_t)tB[0] & kMask);
 #pragma unroll
@@ -63,6 +69,7 @@ struct MontSq {
 #pragma unroll
     for (int l = 1; l < L; ++l) {
       tB[l] = (uint64_t)x0[l] * y1 + tB[l];
+      pin(tB[l]);
       tB[l] = (uint64_t)x1[l] * y0 + tB[l];
     }
     reduce(tA, nq, mA);
@@ -103,7 +110,8 @@ struct MontSq {
 
   // (x0, x1) <- (x0, x1)·(row's digits)·R⁻¹. The first limb block of both digits of `row` arrives in pre
   // (requested during the previous row); the first block of `next` is requested during this row's last
-  // block and leaves in pre. One block of each digit in flight (8 VGPRs; the state leaves no room for two).
+  // block and leaves in pre. One block of each digit in flight (8 VGPRs); two fit in the registers (211
+  // of 256) and measured 1.4 % slower (profiles/foldsq_chainb_ab.txt).
   __device__ __forceinline__ static void mul_row_chain(uint32_t (&x0)[L], uint32_t (&x1)[L], uint32_t (&nq)[L],
                                                        const uint32_t* __restrict__ D, size_t stride,
                                                        const uint32_t* __restrict__ cvec, uint32_t row,
@@ -208,9 +216,14 @@ __global__ void __launch_bounds__(256) k_to_digits(const uint32_t* __restrict__ 
   G g;
   const size_t row = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / TPI;
   if (row >= count) return;
-  uint32_t nq[L], w[L], c[L];
+  uint32_t nq[L], w[L], c[L], hi[L];
   g.load_vec(nq, sq + kSqNq * S);
   g.load_col(w, X, stride, row);
+  // The quotient digits depend only on limbs 0..S-1 (a limb entering the top slot after step i never
+  // reaches the bottom lane's limb 0 within the S steps), so w = REDC_S(X_lo) + X_hi: limbs S..SW-1 are
+  // read once, as a column like the low half (the limbs past SW do not exist: SW <= 2·S), and added
+  // after the loop. Each addend is < 2^W, far inside the lazy bound.
+  g.load_col_narrow(hi, X + (size_t)S * stride, stride, row, SW - S);
   g.load_vec(c, sq + kSqC * S);
   uint64_t tA[L], tB[L];
 #pragma unroll
@@ -221,17 +234,16 @@ __global__ void __launch_bounds__(256) k_to_digits(const uint32_t* __restrict__ 
   const uint32_t kbot = g.bottom ? k : 0u;
 #pragma unroll 4
   for (int i = 0; i < S; ++i) {
-    // limb S + i of the row enters the top slot once step i has moved everything one limb down
-    const uint32_t hi = (g.top && S + i < SW) ? X[(size_t)(S + i) * stride + row] : 0u;
     const uint32_t qa = (uint32_t)tA[0] & kMask;
     const uint32_t mA = grp_bcast0<TPI>(qa);
     tB[0] = (uint64_t)kbot * (kMask - qa) + tB[0];
     const uint32_t mB = grp_bcast0<TPI>((uint32_t)tB[0] & kMask);
     MS::reduce(tA, nq, mA);
     MS::reduce(tB, nq, mB);
-    tA[L - 1] += hi;
     MS::fence(tA, tB);
   }
+#pragma unroll
+  for (int l = 0; l < L; ++l) tA[l] += hi[l];
   M::settle(tA, w, g.bottom);
   M::settle(tB, c, g.bottom);
   M::normalize(w, g.bottom);

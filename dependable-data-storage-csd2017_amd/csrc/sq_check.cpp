@@ -142,8 +142,9 @@ void to_digits(const Ctx& cx, const bn::Limbs& X, Dig& w, Dig& c) {
     const uint32_t mB = (uint32_t)tB.t[0][0] & kMask;
     reduce(tA, cx.nq, qa);
     reduce(tB, cx.nq, mB);
-    if (S + i < SW) tA.add(TPI - 1, L - 1, x[S + i]);
   }
+  // the high half joins after the S steps, limb for limb: w = REDC_S(X_lo) + X_hi
+  for (int j = 0; S + j < SW; ++j) tA.add(j / L, j % L, x[S + j]);
   settle(tA, w);
   settle(tB, c);
   normalize(w);
