@@ -1,4 +1,4 @@
-// Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_opecol.cpp,
+// Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp, ddshe_opecol.cpp,
 // ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp):
 // contexts, stream/buffer pools, per-modulus Montgomery constants, device columns and the
 // orchestration helpers around the HIP kernels. Not part of the public ABI (include/ddshe.h).
@@ -240,7 +240,8 @@ struct PairQueue;  // ddshe_pairs.cpp
 }  // namespace ddshe
 
 
-struct CrtKey;  // CRT form of a Paillier key (ddshe_paillier.cpp)
+struct CrtKey;     // CRT form of a Paillier key (ddshe_paillier.cpp)
+struct RsaCrtKey;  // CRT form of an RSA key (ddshe_rsa.cpp)
 
 struct dds_ctx {
   int device = 0;
@@ -253,6 +254,7 @@ struct dds_ctx {
   std::map<std::pair<ddshe::bn::Limbs, int>, std::shared_ptr<ddshe::host::ModConsts>> mods;
   uint64_t mod_tick = 0;  // LRU clock of mods (under mu)
   std::map<std::pair<ddshe::bn::Limbs, ddshe::bn::Limbs>, std::shared_ptr<CrtKey>> crt_keys;
+  std::map<std::pair<ddshe::bn::Limbs, ddshe::bn::Limbs>, std::shared_ptr<RsaCrtKey>> rsa_keys;
   hipStream_t ext_stream = nullptr;
   std::atomic<bool> timing{false};
   std::mutex tmu;
@@ -587,6 +589,10 @@ int get_mod(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, std::shared_p
 // dds_modmul_fold for an odd modulus, in the shape for max(bits(N), min_bits)
 int modmul_fold_be(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, size_t min_bits, const uint8_t* ops,
                    size_t width, size_t count, uint8_t* out, size_t out_cap, size_t* out_len);
+// out[i] = g^m[i] * x[i]^E mod N on the device with the lane-group ladder (d_m == nullptr: x[i]^E); x rows are
+// rW, fully normalised, < 2N (ddshe_paillier.cpp). Synchronises the stream.
+int modexp_device(Worker* w, hipStream_t st, ModConsts& mc, const bn::Limbs& E, const bn::Limbs* g, const uint32_t* d_x,
+                  size_t xstride, const uint32_t* d_m, size_t count, uint32_t* d_out, size_t ostride);
 int product_tree(dds_ctx* ctx, const std::vector<uint32_t>& h, size_t count, size_t len, size_t cap16, bn::Limbs* out);
 int fold_even_modulus(dds_ctx* ctx, const bn::Limbs& M, const std::vector<bn::Limbs>& xs, const std::vector<bool>& negs,
                       bn::Limbs* out);

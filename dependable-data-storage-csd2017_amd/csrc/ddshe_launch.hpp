@@ -1,4 +1,4 @@
-// Internal launcher interface between the C-ABI's host code (ddshe_capi.cpp, ddshe_paillier.cpp,
+// Internal launcher interface between the C-ABI's host code (ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp,
 // ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -114,6 +114,16 @@ hipError_t launch_modexp_ladder(int S, const uint32_t* Tab, size_t tstride, cons
                                 const uint32_t* consts, const uint32_t* qp_mod, const uint32_t* gR,
                                 const uint32_t* sched, int nsched, uint32_t n0, uint32_t* O, size_t ostride,
                                 hipStream_t st);
+// The same ladder at one bignum per lane (ddshe_ladder1.hpp), without the g^m term: S1 = 20 | 40 limbs of 28
+// bits read from / written to rows of a layout of S >= S1 limbs (limbs [S1, S) of O are zeroed). c1: the
+// constant block of host::ladder1_consts (qp: built with the QP modulus); the table entry j, limb l of a row
+// is Tab[(j*S1 + l)*tstride + row]. DDSHE_LADDER1=0 (ladder1_enabled) keeps the host from choosing it.
+bool ladder1_enabled();
+hipError_t launch_modexp1_pre(int S1, bool qp, const uint32_t* Xcol, size_t xstride, size_t count, const uint32_t* c1,
+                              uint32_t n0, int nodd, uint32_t* Tab, size_t tstride, hipStream_t st);
+hipError_t launch_modexp1_ladder(int S1, bool qp, const uint32_t* Tab, size_t tstride, size_t count,
+                                 const uint32_t* c1, const uint32_t* sched, int nsched, uint32_t n0, uint32_t* O,
+                                 size_t ostride, int S, hipStream_t st);
 // CRT encryption pieces (see ddshe_kernels.hip): radix change between rW layouts (flags[0] |= 1 on
 // overflow), h = (y_p - y_q)(q^2)^-1 mod p^2 (c12 = c1R | c2R, 2*S limbs), c = h*q^2 + y_q
 hipError_t launch_repack(const uint32_t* src, size_t sstride, int Ss, int Ws, uint32_t* dst, size_t dstride, int Sd,

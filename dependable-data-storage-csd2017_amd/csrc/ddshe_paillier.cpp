@@ -41,7 +41,8 @@ struct CrtKey {
   }
 };
 
-namespace {
+namespace ddshe {
+namespace host {
 // out[i] = g^m[i] * x[i]^E mod N on the device (d_m == nullptr: x[i]^E). x rows are rW,
 // fully normalised, < 2N. Processes the batch in equal chunks so the per-row window table
 // (nodd * S words per row) stays within kModexpTabBytes of HBM.
@@ -78,7 +79,10 @@ int modexp_device(Worker* w, hipStream_t st, ModConsts& mc, const bn::Limbs& E, 
   HIP_TRY(hipStreamSynchronize(st));  // host vectors above must outlive the async copies
   return DDS_OK;
 }
+}  // namespace host
+}  // namespace ddshe
 
+namespace {
 int encrypt_device(Worker* w, hipStream_t st, ModConsts& mc, const bn::Limbs& n, const bn::Limbs& g,
                    const uint32_t* d_m, const uint32_t* d_rcol, size_t rstride, size_t count, uint32_t* d_out,
                    size_t ostride, bool use_n_exponent) {

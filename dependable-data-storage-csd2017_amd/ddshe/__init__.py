@@ -65,6 +65,7 @@ EXPORTS = [
     "dds_strtab_stats", "dds_strtab_truncate", "dds_host_register", "dds_host_unregister", "dds_host_alloc",
     "dds_host_free", "dds_paillier_decrypt_batch_crt", "dds_col_decrypt_paillier",
     "dds_col_dec_width", "dds_col_read_dec", "dds_paillier_encrypt_batch_dec",
+    "dds_rsa_decrypt_batch_crt", "dds_col_decrypt_rsa", "dds_rsa_crt_plan",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -146,6 +147,11 @@ _sig("dds_paillier_decrypt_batch_crt", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c
      C.c_char_p, _sz, _sz, _u8p, _sz)
 _sig("dds_col_decrypt_paillier", C.c_int, C.c_void_p, _sz, _sz, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz,
      _u8p, _sz)
+_sig("dds_rsa_decrypt_batch_crt", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz,
+     C.c_char_p, _sz, _sz, _u8p, _sz)
+_sig("dds_col_decrypt_rsa", C.c_int, C.c_void_p, _sz, _sz, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz,
+     _u8p, _sz)
+_sig("dds_rsa_crt_plan", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, C.POINTER(C.c_int), C.POINTER(C.c_int))
 _sig("dds_modexp_batch", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz, _sz, _u8p)
 for _n in ("dds_sum_all_dec", "dds_mult_all_dec"):
     _sig(_n, C.c_int, C.c_void_p, C.POINTER(C.c_char_p), _sz, C.c_char_p, C.c_char_p, _sz, _szp)
@@ -527,6 +533,25 @@ class Engine:
         raw = bytes(out)
         return [int.from_bytes(raw[i * nb:(i + 1) * nb], "big") for i in range(len(cs))]
 
+    def rsa_decrypt_batch_crt(self, p: int, q: int, d: int, cs) -> list[int]:
+        """HomoMult.decrypt(priv, c) = c^d mod p*q for each c in cs (values in [0, p*q)) through the CRT halves."""
+        cs = [int(c) for c in cs]
+        nb, cw = nbytes(p * q), max([1] + [nbytes(c) for c in cs])
+        out = (C.c_uint8 * (nb * max(1, len(cs))))()
+        _check(_lib.dds_rsa_decrypt_batch_crt(self._h, int_to_be(p, nbytes(p)), nbytes(p), int_to_be(q, nbytes(q)),
+                                              nbytes(q), int_to_be(d, nbytes(d)), nbytes(d), ints_to_be(cs, cw), cw,
+                                              len(cs), out, nb), "dds_rsa_decrypt_batch_crt")
+        raw = bytes(out)
+        return [int.from_bytes(raw[i * nb:(i + 1) * nb], "big") for i in range(len(cs))]
+
+    def rsa_crt_plan(self, p: int, q: int) -> tuple:
+        """dds_rsa_crt_plan: ((s1_p, qp_p), (s1_q, qp_q)); s1 = 20 | 40 (one bignum per lane), 0 (lane groups),
+        -1 (full width over n); qp: that ladder reduces against N*n'. No GPU work."""
+        s1, qp = (C.c_int * 2)(), (C.c_int * 2)()
+        _check(_lib.dds_rsa_crt_plan(self._h, int_to_be(p, nbytes(p)), nbytes(p), int_to_be(q, nbytes(q)), nbytes(q),
+                                     s1, qp), "dds_rsa_crt_plan")
+        return ((s1[0], bool(qp[0])), (s1[1], bool(qp[1])))
+
     def modexp_batch(self, modulus: int, exponent: int, bases) -> list[int]:
         """out[i] = bases[i]^exponent mod modulus (HomoMult.encrypt for an RSA key)."""
         bases = [int(x) for x in bases]
@@ -766,6 +791,20 @@ class Column(_Mutable):
 
     def decrypt_paillier(self, first: int, count: int, p: int, q: int, g: int) -> list[int]:
         return [int.from_bytes(r.tobytes(), "big") for r in self.decrypt_paillier_buffer(first, count, p, q, g)]
+
+    def decrypt_rsa_buffer(self, first: int, count: int, p: int, q: int, d: int,
+                           n_bytes: int | None = None) -> np.ndarray:
+        """HomoMult.decrypt of rows [first, first+count) of a column over p*q (dds_col_decrypt_rsa): big-endian
+        values c^d mod p*q, uint8 [count, n_bytes] (n_bytes defaults to the byte length of p*q)."""
+        nb = nbytes(p * q) if n_bytes is None else n_bytes
+        out = np.empty((max(1, count), max(1, nb)), dtype=np.uint8)
+        _check(_lib.dds_col_decrypt_rsa(self._h, first, count, int_to_be(p, nbytes(p)), nbytes(p),
+                                        int_to_be(q, nbytes(q)), nbytes(q), int_to_be(d, nbytes(d)), nbytes(d),
+                                        out.ctypes.data_as(_u8p), nb), "dds_col_decrypt_rsa")
+        return out[:count]
+
+    def decrypt_rsa(self, first: int, count: int, p: int, q: int, d: int) -> list[int]:
+        return [int.from_bytes(r.tobytes(), "big") for r in self.decrypt_rsa_buffer(first, count, p, q, d)]
 
 
 OPE_CLS_LACKS, OPE_CLS_LAST, OPE_CLS_INNER = 0, 1, 2

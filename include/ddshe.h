@@ -455,6 +455,34 @@ int dds_col_decrypt_paillier(dds_col* col, size_t first, size_t count, const uin
                              const uint8_t* q_be, size_t q_bytes, const uint8_t* g_be, size_t g_bytes,
                              uint8_t* out, size_t n_bytes);
 
+/* HomoMult.decrypt(priv, c) = c^d mod n (SJHomoLibProvider.scala:69), n = p*q, for `count` ciphertexts
+ * (big-endian, `width` bytes each, values in [0, n): DDS_E_RANGE otherwise) with the factors of the
+ * RSAPrivateCrtKey the client holds (:26, :48). out: count values < n, n_bytes each, big-endian. p, q in either
+ * order. Computed as u_p = c^(d_p) mod p and u_q = c^(d_q) mod q with d_f = d mod (f-1), replaced by f-1 when
+ * that is 0 and d > 0, then Garner's recombination m = u_q + q ((u_p - u_q) q^-1 mod p): equal to c^d mod n
+ * for EVERY c in [0, n) and every d >= 0, whether or not c is coprime to n (d = 0 gives 1 mod n).
+ * n_bytes below the byte length of n: DDS_E_BUFSIZE; p, q not distinct odd primes: DDS_E_ARG. Which ladder
+ * runs: dds_rsa_crt_plan; every choice gives the same bytes. After an error the contents of out are
+ * unspecified. With dds_ctx_set_timing on, a call adds the device time of its kernels to total_ms and that
+ * of its exponentiation ladders to fold_ms. */
+int dds_rsa_decrypt_batch_crt(dds_ctx*, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be, size_t q_bytes,
+                              const uint8_t* d_be, size_t d_bytes, const uint8_t* c_be, size_t width, size_t count,
+                              uint8_t* out, size_t n_bytes);
+/* The same for rows [first, first+count) of a resident column over n = p*q (positional, like dds_col_read);
+ * a column over another modulus, or rows past the last one: DDS_E_ARG, before any GPU work. */
+int dds_col_decrypt_rsa(dds_col* col, size_t first, size_t count, const uint8_t* p_be, size_t p_bytes,
+                        const uint8_t* q_be, size_t q_bytes, const uint8_t* d_be, size_t d_bytes, uint8_t* out,
+                        size_t n_bytes);
+/* Which ladder a key's factors get (index 0: p, 1: q): s1[i] = 20 | 40 (one bignum per lane at that many
+ * 28-bit limbs), 0 (lane groups, in the factor's own shape or the next that holds the halves of c), -1 (no CRT:
+ * full width over n with d); qp[i] != 0 where that ladder reduces against N*n'. c (below 2n, B = bits(n) + 1
+ * bits) is split at limb j = ceil(B / 2W) of the n layout; with h the longer half, both factors take the
+ * smallest S1 of 20, 40 with 28 S1 - 2 >= max(h, bits(p), bits(q)) (QP where 28 S1 >= bits(factor) + 30), else
+ * lane groups when h fits each factor's shape or is at most bits(factor) + 64, else -1. DDSHE_LADDER1=0 in the
+ * environment rules the one-bignum-per-lane ladder out. No GPU work. */
+int dds_rsa_crt_plan(dds_ctx*, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be, size_t q_bytes, int s1[2],
+                     int qp[2]);
+
 /* Batched modular exponentiation out[i] = base[i]^exp mod modulus (mod_bytes each):
  * HomoMult.encrypt(pk, m) = m^e mod n (SJHomoLibProvider.scala:59) and decrypt-side
  * checks. Bases are validated like fold operands. */
