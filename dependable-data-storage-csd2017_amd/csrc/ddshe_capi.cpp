@@ -141,7 +141,7 @@ int get_mod(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, std::shared_p
     if (hipMemcpy(mc->d3, h3.data(), h3.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
       return fail(DDS_E_HIP, "const upload");
   }
-  if (fold_qp_enabled() && (size_t)mc->W * S >= bn::bit_length(nq) + 2) {
+  if ((size_t)mc->W * S >= bn::bit_length(nq) + 2) {
     if (int rc = upload_qp(S, &mc->dqm)) return rc;
     mc->qbound = nq;  // level-1 partials are then < 2N~ too
   }
@@ -233,48 +233,19 @@ size_t max_fold_groups(dds_ctx* ctx, int S) {
 }
 
 // The reduction tree after the first fold level (ddshe_tree.hip: workgroup-cooperative Montgomery
-// products, one launch per level). Default on: faster than round 1's per-level lane-group launches at
-// every fold size measured (tools/tree_ab.py); DDSHE_TREE=0 selects those (k_fold in the
-// tail shape + k_finalize) for A/B runs. DDSHE_TREE_DIRECT (rows, default 2048): folds up to that many
-// rows skip the first level and run the tree over the rows themselves (when the tree's R3 covers raw
-// rows, ModConsts::tree_direct).
-bool use_tree() {
-  static const bool on = [] {
-    const char* e = getenv("DDSHE_TREE");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-size_t tree_direct_rows() {
-  static const size_t n = [] {
-    const char* e = getenv("DDSHE_TREE_DIRECT");
-    return e ? (size_t)atoll(e) : (size_t)2048;
-  }();
-  return n;
-}
-// DDSHE_TREE_SWITCH (leaves, default 4096): wider levels run as tail-shape lane-group launches (many
-// products per launch: throughput), the last log2(switch) levels as tree launches (one workgroup per
-// product: latency; the widest of them on 256-thread workgroups, ddshe_tree.hip). Round 3 A/B
-// (tools/tree_sweep.sh, profiles/r03_tree_plan_sweep.txt): with the 256-thread wide levels and
-// in-kernel hand-offs, 1024 -> 4096 takes a 10k-row fold of the 1024-bit key 0.092 -> 0.088 ms and
-// of the 2048-bit key 0.141 -> 0.129 ms; 10M-row folds within noise.
-size_t tree_switch_leaves() {
-  static const size_t n = [] {
-    const char* e = getenv("DDSHE_TREE_SWITCH");
-    return e ? (size_t)atoll(e) : (size_t)4096;
-  }();
-  return n;
-}
-
-// DDSHE_NARROW_ROWS (rows, default 65536; 0 disables): folds of up to that many rows run their first
-// level in the latency (tail) shape, one product per group, straight from the main-shape rows
-size_t narrow_fold_rows() {
-  static const size_t n = [] {
-    const char* e = getenv("DDSHE_NARROW_ROWS");
-    return e ? (size_t)atoll(e) : (size_t)65536;
-  }();
-  return n;
-}
+// products). Folds of up to kTreeDirectRows rows skip the first level and run the tree over the rows
+// themselves (when the tree's R3 covers raw rows, ModConsts::tree_direct).
+constexpr size_t kTreeDirectRows = 2048;
+// Levels wider than kTreeSwitchLeaves leaves run as tail-shape lane-group launches (many products per
+// launch: throughput), the last log2(kTreeSwitchLeaves) levels as tree launches (one workgroup per
+// product: latency; the widest of them on 256-thread workgroups, ddshe_tree.hip). Swept in round 3
+// (profiles/r03_tree_plan_sweep.txt): with the 256-thread wide levels and in-kernel hand-offs,
+// 1024 -> 4096 takes a 10k-row fold of the 1024-bit key 0.092 -> 0.088 ms and of the 2048-bit key
+// 0.141 -> 0.129 ms; 10M-row folds within noise.
+constexpr size_t kTreeSwitchLeaves = 4096;
+// Folds of up to kNarrowFoldRows rows run their first level in the latency (tail) shape, one product per
+// group, straight from the main-shape rows
+constexpr size_t kNarrowFoldRows = 65536;
 
 FoldDigits col_fold_digits(dds_col* col, hipStream_t st, size_t first, size_t count, const uint32_t* d_ids) {
   ModConsts& mc = *col->mc;
@@ -305,11 +276,10 @@ FoldDigits col_fold_digits(dds_col* col, hipStream_t st, size_t first, size_t co
 // digits (col_fold_digits): level 1 runs in digit form (k_fold_sq) and k_sq_join hands the tail the same
 // leaves k_fold would, with another power of two.
 int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
-                size_t count, const uint32_t* d_ids, Leaves* lv, size_t max_groups, const FoldDigits& dg) {
+                size_t count, const uint32_t* d_ids, Leaves* lv, const FoldDigits& dg) {
   const int S = mc.S, S2 = mc.S2;
   if (dg.D && !d_ids && mc.sq && count >= 2) {
-    size_t gmax = fold_sq_max_groups(ctx->cus);
-    if (max_groups) gmax = std::min(gmax, max_groups);
+    const size_t gmax = fold_sq_max_groups(ctx->cus);
     const size_t G = std::min(gmax, std::max<size_t>(1, count / 2)), ps = round_up(G, 64);
     HIP_TRY(w->p0.ensure((size_t)S2 * ps * 4));
     HIP_TRY(w->sqp.ensure((size_t)2 * kFoldSqLimbs * ps * 4));
@@ -328,14 +298,14 @@ int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const ui
                  -(int64_t)mc.W * kFoldSqLimbs * (2 * (int64_t)count - (int64_t)G), nullptr};
     return DDS_OK;
   }
-  if (use_tree() && mc.tree_direct && count <= tree_direct_rows()) {
+  if (mc.tree_direct && count <= kTreeDirectRows) {
     *lv = Leaves{X, xstride, S, mc.W, count, 0, d_ids};
     return DDS_OK;
   }
   // small folds: the first level in the latency shape S2 straight from the rows (one product per group)
-  if (!d_ids && S2 > S && S % 4 == 0 && fold_narrow_shape(S2) && count <= narrow_fold_rows()) {
+  if (!d_ids && S2 > S && S % 4 == 0 && fold_narrow_shape(S2) && count <= kNarrowFoldRows) {
     const size_t G = std::max<size_t>(1, count / 2), ps = round_up(G, 64);
-    const bool rowmajor = use_tree() && G <= tree_switch_leaves();  // straight to the tree
+    const bool rowmajor = G <= kTreeSwitchLeaves;  // straight to the tree
     HIP_TRY(w->p0.ensure((size_t)S2 * ps * 4));
     HIP_TRY(launch_fold_narrow(S2, X, xstride, count, S, mc.d2, mc.dq, mc.n0, w->p0.as<uint32_t>(), rowmajor ? 1 : ps,
                                G, st, rowmajor ? (size_t)S2 : 1));
@@ -352,37 +322,9 @@ int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const ui
     if (fold1_occupancy(S1, &bpc) != hipSuccess || bpc < 1) bpc = 1;
     gmax = (size_t)ctx->cus * bpc * 256;
   }
-  if (max_groups) gmax = std::min(gmax, max_groups);
-  size_t G = std::min(gmax, std::max<size_t>(1, count / 2));
-  size_t ps = round_up(G, 64);
+  const size_t G = std::min(gmax, std::max<size_t>(1, count / 2));
+  const size_t ps = round_up(G, 64);
   HIP_TRY(w->p0.ensure((size_t)S2 * ps * 4));
-  // DDSHE_FOLD_INBLOCK=1 (A/B, off by default): level 1 with the in-block tree (k_fold InBlock), one
-  // row-major leaf per block straight to the reduction tree instead of the tail launches that take the
-  // G partials down to tree_switch_leaves(). Measured slower (profiles/r06_inblock_ab.txt: headline
-  // level 1 14.6 -> 15.7 ms, the strong-split share 1.75 -> 2.11 ms): the in-block products run in the
-  // throughput shape (4 lanes per bignum), whose per-product latency is ~4x the tail shape's.
-  static const int inblock = [] {
-    const char* e = getenv("DDSHE_FOLD_INBLOCK");
-    return e ? atoi(e) : 0;
-  }();
-  const size_t gpb = 256 / (size_t)pick_tpi(S);
-  const size_t Gb = G / gpb * gpb;  // whole blocks of live groups
-  if (inblock && use_tree() && !S1 && !d_ids && mc.dqm && S2 >= S && Gb > tree_switch_leaves()) {
-    G = Gb;
-    const size_t B = G / gpb;
-    record_time(ctx, w, st, true, 0);
-    HIP_TRY(launch_fold(S, X, xstride, count, mc.d, mc.dqm, mc.n0, w->p0.as<uint32_t>(), 1, G, S2, st, nullptr, 0,
-                        (size_t)S2));
-    record_time(ctx, w, st, false, 0);
-    if (ctx->timing.load()) {
-      w->timed_fold = true;
-      std::lock_guard<std::mutex> lk(ctx->tmu);
-      ctx->pending_modmuls = count - B;  // the row products and the in-block ones
-    }
-    *lv = Leaves{w->p0.as<uint32_t>(), 1, S2, mc.W, B, (int64_t)mc.W * S * ((int64_t)B - (int64_t)count), nullptr,
-                 (size_t)S2};
-    return DDS_OK;
-  }
   record_time(ctx, w, st, true, 0);
   HIP_TRY(launch_fold(S, X, xstride, count, mc.d, mc.dqm, mc.n0, w->p0.as<uint32_t>(), ps, G, S2, st, d_ids, S1));
   record_time(ctx, w, st, false, 0);
@@ -402,56 +344,15 @@ int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const ui
 int reduce_leaves(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const Leaves& lv, bool finalize,
                   bn::Limbs* value, const uint32_t** part, int64_t* Eout) {
   const int S2 = mc.S2;
-  if (!use_tree()) {  // round 1: one launch per level in the tail shape, then k_finalize
-    if (lv.Sin != S2 || lv.ids) return fail(DDS_E_ARG, "tail levels need leaves in the tail shape");
-    HIP_TRY(w->p1.ensure((size_t)S2 * round_up((lv.n + 1) / 2, 64) * 4));
-    HIP_TRY(w->x2.ensure((size_t)S2 * round_up((lv.n + 1) / 2, 64) * 4));
-    const uint32_t* cur = lv.X;
-    uint32_t* bufs[2] = {w->p1.as<uint32_t>(), w->x2.as<uint32_t>()};
-    size_t n = lv.n, cs = lv.xs;
-    int flip = 0;
-    while (n > 1) {
-      size_t ng = (n + 1) / 2, ns = round_up(ng, 64);
-      HIP_TRY(launch_fold_tail(S2, cur, cs, n, mc.d2, mc.dq, mc.n0, bufs[flip], ns, ng, st));
-      cur = bufs[flip];
-      flip ^= 1;
-      n = ng;
-      cs = ns;
-    }
-    const int64_t E = lv.E - mc.wS2() * ((int64_t)lv.n - 1);
-    if (!finalize) {  // partial: S2 limbs at stride cs -> consecutive
-      HIP_TRY(w->out.ensure((size_t)S2 * 4));
-      HIP_TRY(launch_strided_copy(cur, 0, cs, w->out.as<uint32_t>(), 0, 1, 1, S2, st));
-      *part = w->out.as<uint32_t>();
-      *Eout = E;
-      return DDS_OK;
-    }
-    uint32_t* hy = nullptr;  // pinned: [0, S2) Y, [S2, 2 S2) result
-    HIP_TRY(stage_ptr(w, &hy));
-    hy += kStageWord0;
-    {
-      const std::vector<uint32_t>& y = mc.y_for(E);
-      std::copy(y.begin(), y.end(), hy);
-    }
-    HIP_TRY(w->y.ensure((size_t)S2 * 4));
-    HIP_TRY(w->out.ensure((size_t)S2 * 4));
-    HIP_TRY(hipMemcpyAsync(w->y.p, hy, (size_t)S2 * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(launch_finalize_tail(S2, cur, cs, mc.d2, w->y.as<uint32_t>(), mc.n0, w->out.as<uint32_t>(), st));
-    HIP_TRY(hipMemcpyAsync(hy + S2, w->out.p, (size_t)S2 * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    account_fold(ctx, w);
-    *value = mc.value2(hy + S2);
-    return DDS_OK;
-  }
   Leaves lt = lv;
-  if (lv.Sin == S2 && !lv.ids && lv.gs == 1 && lv.n > tree_switch_leaves()) {  // wide levels: tail-shape launches
+  if (lv.Sin == S2 && !lv.ids && lv.gs == 1 && lv.n > kTreeSwitchLeaves) {  // wide levels: tail-shape launches
     HIP_TRY(w->p1.ensure((size_t)S2 * round_up((lv.n + 1) / 2, 64) * 4));
     HIP_TRY(w->x2.ensure((size_t)S2 * round_up((lv.n + 1) / 2, 64) * 4));
     uint32_t* bufs[2] = {w->p1.as<uint32_t>(), w->x2.as<uint32_t>()};
     int flip = 0;
-    while (lt.n > tree_switch_leaves()) {
+    while (lt.n > kTreeSwitchLeaves) {
       const size_t ng = (lt.n + 1) / 2, ns = round_up(ng, 64);
-      const bool rowmajor = ng <= tree_switch_leaves();  // the last lane-group level: the tree's leaf layout
+      const bool rowmajor = ng <= kTreeSwitchLeaves;  // the last lane-group level: the tree's leaf layout
       HIP_TRY(launch_fold_tail(S2, lt.X, lt.xs, lt.n, mc.d2, mc.dq, mc.n0, bufs[flip], rowmajor ? 1 : ns, ng, st,
                                rowmajor ? (size_t)S2 : 1));
       lt.E -= mc.wS2() * (int64_t)(lt.n - ng);  // n - ng products, R2^-1 each
@@ -549,14 +450,8 @@ int reduce_leaves(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const 
 int fold_partial_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
                         size_t count, const uint32_t** part, size_t* part_stride, int64_t* E, const uint32_t* d_ids,
                         const FoldDigits& dg) {
-  // DDSHE_PARTIAL_GROUPS (A/B of the strong-split share): cap level 1's groups so the
-  // share's partials go straight to the tree (<= 4096) instead of through the tail launches
-  static const size_t cap = [] {
-    const char* e = getenv("DDSHE_PARTIAL_GROUPS");
-    return e ? (size_t)atoll(e) : (size_t)0;
-  }();
   Leaves lv;
-  int rc = fold_level1(ctx, w, st, mc, X, xstride, count, d_ids, &lv, cap, dg);
+  int rc = fold_level1(ctx, w, st, mc, X, xstride, count, d_ids, &lv, dg);
   if (rc) return rc;
   *part_stride = 1;
   return reduce_leaves(ctx, w, st, mc, lv, false, nullptr, part, E);
@@ -565,7 +460,7 @@ int fold_partial_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, 
 int fold_value_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
                       size_t count, const uint32_t* d_ids, bn::Limbs* value, const FoldDigits& dg) {
   Leaves lv;
-  int rc = fold_level1(ctx, w, st, mc, X, xstride, count, d_ids, &lv, 0, dg);
+  int rc = fold_level1(ctx, w, st, mc, X, xstride, count, d_ids, &lv, dg);
   if (rc) return rc;
   lv.rows = count;
   return reduce_leaves(ctx, w, st, mc, lv, true, value, nullptr, nullptr);

@@ -99,16 +99,10 @@ struct Mont {
     // pass 1: t += a*b, in place (no 64-bit temporaries live across the pass). The
     // quotient m depends only on limb 0, so it is issued first and its latency
     // (mul_lo -> and -> DPP) hides under the remaining L-1 mads.
-#ifndef DDSHE_AB_M_LATE
     t[0] = (uint64_t)a[0] * b + t[0];
     const uint32_t m = grp_bcast0<TPI>((QP ? (uint32_t)t[0] : (uint32_t)t[0] * n0) & kMask);
 #pragma unroll
     for (int l = 1; l < L; ++l) t[l] = (uint64_t)a[l] * b + t[l];
-#else
-#pragma unroll
-    for (int l = 0; l < L; ++l) t[l] = (uint64_t)a[l] * b + t[l];
-    const uint32_t m = grp_bcast0<TPI>(((uint32_t)t[0] * n0) & kMask);
-#endif
     // pass 2: t = (t + m*N) / 2^W, shifting down one limb in place
     const uint64_t u0 = (uint64_t)m * n[0] + t[0];
     const uint32_t lo0 = (uint32_t)u0 & kMask;  // == 0 on the group's lane 0
@@ -141,9 +135,6 @@ struct Mont {
   // opaque register barrier: stops LLVM re-associating the u64 sums of consecutive
   // unrolled steps into mad(x,y,0)+add trees (extra registers and 64-bit adds)
   __device__ __forceinline__ static void fence_t(uint64_t (&t)[L]) {
-#ifdef DDSHE_AB_NO_FENCE_T
-    return;
-#endif
 #pragma unroll
     for (int l = 0; l < L; ++l) asm volatile("" : "+v"(t[l]));
   }
@@ -151,9 +142,6 @@ struct Mont {
   // from hoisting zext(a[l]) / zext(n[l]) out of the step loop as 64-bit values, which
   // would pin every operand to an even register and waste ~2L VGPRs
   __device__ __forceinline__ static void fence_ops(uint32_t (&a)[L], const uint32_t (&n)[L]) {
-#ifdef DDSHE_AB_NO_FENCE_OPS
-    return;
-#endif
 #pragma unroll
     for (int l = 0; l < L; ++l) asm volatile("" : "+v"(a[l]));
     if constexpr (TPI == 1) {  // N is wave-uniform: keep it in SGPRs (one SGPR operand per mad)
@@ -180,11 +168,7 @@ struct Mont {
     uint64_t t[L];
 #pragma unroll
     for (int l = 0; l < L; ++l) t[l] = 0;
-#ifdef DDSHE_AB_PF
-    constexpr int PF = DDSHE_AB_PF;
-#else
     constexpr int PF = (S % 4 == 0) ? 4 : 2;  // limbs per unrolled block = loads in flight
-#endif
     static_assert(S % PF == 0 && S >= 2 * PF, "S % PF");
     const uint32_t voff = row * 4u;
     const uint32_t sstride = (uint32_t)stride * 4u;  // host guarantees PF*stride*4 < 2^32
@@ -192,7 +176,6 @@ struct Mont {
       return __builtin_amdgcn_make_buffer_rsrc((void*)(X + (size_t)i * stride), (short)0, (int)(PF * sstride),
                                                0x00020000);
     };
-#ifndef DDSHE_AB_SHALLOW_PF
     // two blocks in flight: limbs of block i+2 are requested while block i is computed
     // (one block = PF steps ~ 1.4k cycles per wave is short of an HBM miss under load)
     uint32_t bq[PF], bm[PF];
@@ -231,34 +214,6 @@ struct Mont {
       step(t, a, n, bm[q], n0, top);
       fence_t(t);
     }
-#else
-    uint32_t bq[PF];
-    {
-      const auto rs = block_rsrc(0);
-#pragma unroll
-      for (int q = 0; q < PF; ++q) bq[q] = __builtin_amdgcn_raw_buffer_load_b32(rs, voff, q * sstride, 0);
-    }
-#pragma unroll 1
-    for (int i = 0; i < S - PF; i += PF) {
-      if constexpr (FenceOps) fence_ops(a, n);
-      const auto rs = block_rsrc(i + PF);
-      uint32_t bn[PF];
-#pragma unroll
-      for (int q = 0; q < PF; ++q) bn[q] = __builtin_amdgcn_raw_buffer_load_b32(rs, voff, q * sstride, 0);
-#pragma unroll
-      for (int q = 0; q < PF; ++q) {
-        step(t, a, n, bq[q], n0, top);
-        fence_t(t);
-      }
-#pragma unroll
-      for (int q = 0; q < PF; ++q) bq[q] = bn[q];
-    }
-#pragma unroll
-    for (int q = 0; q < PF; ++q) {
-      step(t, a, n, bq[q], n0, top);
-      fence_t(t);
-    }
-#endif
     settle(t, a, bottom);
   }
 

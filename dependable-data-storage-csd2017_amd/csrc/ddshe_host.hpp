@@ -161,7 +161,6 @@ struct ModConsts {
   uint32_t* dsq = nullptr;
   std::map<int64_t, std::vector<uint32_t>> y3cache;  // E -> 2^(W3*S3 - E) mod N, tree limbs
   std::mutex ymu;
-  std::map<int64_t, std::vector<uint32_t>> ycache;  // E -> 2^(W*S2 - E) mod N, tail limbs
   // decimal codec table (k_dec_parse), built on first use: Pt[l*jpad + j] = limb l of 10^(8j)
   // for the jfit powers below 2^(W*S), then jst[i] (first power reaching limb TPI*i, rounded down to 4)
   std::mutex decmu;
@@ -184,17 +183,8 @@ struct ModConsts {
   bn::Limbs pow2(int64_t e) const {
     return e >= 0 ? bn::powmod_u64(bn::Limbs{2}, (uint64_t)e, N) : bn::powmod_u64(half, (uint64_t)(-e), N);
   }
-  // finalize multiplier for a tail-shape partial holding prod * 2^E. Returned BY VALUE: the cache
+  // finalize multiplier of the reduction tree for a root holding prod * 2^E. Returned BY VALUE: the cache
   // may be cleared by a concurrent caller while this one's async copy still reads its vector.
-  std::vector<uint32_t> y_for(int64_t E) {
-    std::lock_guard<std::mutex> lk(ymu);
-    auto it = ycache.find(E);
-    if (it != ycache.end()) return it->second;
-    if (ycache.size() >= 64) ycache.clear();
-    bn::Limbs y = pow2((int64_t)W * S2 - E);
-    return ycache.emplace(E, bn::to_rw(y, S2, W)).first->second;
-  }
-  // finalize multiplier of the reduction tree for a root holding prod * 2^E (by value, as y_for)
   std::vector<uint32_t> y3_for(int64_t E) {
     std::lock_guard<std::mutex> lk(ymu);
     auto it = y3cache.find(E);
@@ -627,8 +617,7 @@ struct FoldDigits {
 // then runs as before). Caller holds col->mu (shared or exclusive). May synchronise the stream.
 FoldDigits col_fold_digits(dds_col* col, hipStream_t st, size_t first, size_t count, const uint32_t* d_ids);
 int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
-                size_t count, const uint32_t* d_ids, Leaves* lv, size_t max_groups = 0,
-                const FoldDigits& dg = FoldDigits());
+                size_t count, const uint32_t* d_ids, Leaves* lv, const FoldDigits& dg = FoldDigits());
 int reduce_leaves(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const Leaves& lv, bool finalize,
                   bn::Limbs* value, const uint32_t** part, int64_t* Eout);
 // canonical product of `count` rows (rows d_ids[0..count) when given); synchronises the stream

@@ -4,9 +4,9 @@
 //   X[l * stride + row], l in [0, S), stride >= rows (multiple of 64),
 // so that the lanes of a wave touch consecutive rows of one limb (coalesced).
 //
-// Reference operations accelerated (all in /root/reference/src/main/scala/):
-//   SumAll fold   dds/http/DDSRestServer.scala:397-446  -> k_fold + k_finalize
-//   MultAll fold  dds/http/DDSRestServer.scala:491-539  -> k_fold + k_finalize
+// Reference operations accelerated (all in the reference's src/main/scala/):
+//   SumAll fold   dds/http/DDSRestServer.scala:397-446  -> k_fold / k_fold1 / k_fold_sq + k_tree (ddshe_tree.hip)
+//   MultAll fold  dds/http/DDSRestServer.scala:491-539  -> k_fold / k_fold1 + k_tree
 //   Sum / Mult    dds/http/DDSRestServer.scala:355-395, 447-490 -> k_pairs
 //   Search{Gt,GtEq,Lt,LtEq} DDSRestServer.scala:682-830 -> k_ope_count + k_ope_scatter
 //   HomoAdd.encrypt  utils/SJHomoLibProvider.scala:58 -> k_modexp_pre + k_modexp_ladder (also HomoMult.encrypt, :59)
@@ -323,16 +323,11 @@ __global__ void __launch_bounds__(256, 2) k_modexp_pre(const uint32_t* __restric
 // leaves the Montgomery form below 2N (R > 2N~) for the canonical reduction.
 // Occupancy: one S-word LDS slot per group (x^E·R is parked in the group's output row in HBM while
 // g^m is computed, not in a second slot) and at most 168 VGPRs, so three waves per SIMD hide the
-// squarings' serial parts (the LDS round trip of the operand, the settle/normalise carry chains);
-// DDSHE_LADDER_OCC2=1 builds the previous two-wave form (two slots, 172 VGPRs) for A/B.
+// squarings' serial parts (the LDS round trip of the operand, the settle/normalise carry chains).
 // Shapes of more than 29 limbs per lane keep two waves (a 168-VGPR bound spills them heavily).
 template <int S, int TPI>
 constexpr int ladder_waves() {
-#ifdef DDSHE_LADDER_OCC2
-  return 2;
-#else
   return S / TPI <= 29 ? 3 : 2;
-#endif
 }
 template <int S, int TPI, int W, bool QP = false>
 __global__ void __launch_bounds__(256, (ladder_waves<S, TPI>())) k_modexp_ladder(const uint32_t* __restrict__ Tab, size_t tstride,
@@ -349,12 +344,7 @@ __global__ void __launch_bounds__(256, (ladder_waves<S, TPI>())) k_modexp_ladder
   G g;
   const size_t grp = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / TPI;
   if (grp >= count) return;
-#ifdef DDSHE_LADDER_OCC2
-  uint32_t* sq = lds + (size_t)(threadIdx.x / TPI) * 2 * S;  // group-private operand slots
-  uint32_t* xs = sq + S;
-#else
   uint32_t* sq = lds + (size_t)(threadIdx.x / TPI) * S;  // group-private operand slot
-#endif
   uint32_t n[L], acc[L];
   g.load_vec(n, QP ? qp_mod : consts + kConstN * S);
   if (nsched > 0) g.load_col(acc, Tab + (size_t)sched[0] * S * tstride, tstride, grp);
@@ -377,14 +367,13 @@ __global__ void __launch_bounds__(256, (ladder_waves<S, TPI>())) k_modexp_ladder
     uint32_t wb = mi ? 32u - (uint32_t)__builtin_clz(mi) : 0u;
     for (int off = 32; off >= 1; off >>= 1) wb = max(wb, (uint32_t)__shfl_xor((int)wb, off));
     M::normalize(acc, g.bottom);
-#ifdef DDSHE_LADDER_OCC2
-    store_lds<S, TPI, W>(xs, acc, g.r);  // park x^E*R in xs; acc is reused for g^m
-#else
     // park x^E*R in this group's output row (read back by mul_col below: other lanes' limbs, so the
-    // stores must have landed — workgroup fence: vmcnt(0), the write-through L1 serves the reloads)
+    // stores must have landed — workgroup fence: vmcnt(0), the write-through L1 serves the reloads).
+    // Assumption: the re-read relies on workgroup-scope visibility of other lanes' stores through the
+    // vector L1, which holds only when the kernel is not built in threadgroup-split mode (the waves of a
+    // workgroup then share one CU and its L1; this library is never built that way).
     g.store_col(acc, O, ostride, grp);
     __threadfence_block();
-#endif
     g.load_vec(acc, consts + kConstRmod * S);
     for (int i = (int)wb - 1; i >= 0; --i) {
       M::normalize(acc, g.bottom);
@@ -396,11 +385,7 @@ __global__ void __launch_bounds__(256, (ladder_waves<S, TPI>())) k_modexp_ladder
       M::mul_lds(acc, n, sq, n0, g.top, g.bottom);
     }
     // acc = (g^m R) * (x^E R) * R^-1
-#ifdef DDSHE_LADDER_OCC2
-    M::mul_lds(acc, n, xs, n0, g.top, g.bottom);
-#else
     M::mul_col(acc, n, O, ostride, (uint32_t)grp, n0, g.top, g.bottom);
-#endif
   }
   if constexpr (QP) g.load_vec(n, consts + kConstN * S);
   Mont<S, TPI, W>::mul_col(acc, n, consts + kConstOne * S, 1, 0, n0, g.top, g.bottom);  // leave Montgomery form
@@ -708,7 +693,7 @@ __device__ __forceinline__ uint32_t ope_thread_mask(const int64_t* __restrict__ 
 // past the buffer's end (the last tile's) are dropped
 __device__ __forceinline__ void ope_store_mask(uint32_t m, uint32_t* __restrict__ masks, uint32_t* __restrict__ counts,
                                                size_t tile, unsigned long long* __restrict__ total = nullptr,
-                                               size_t hlimit = 0, int hwide = 0) {
+                                               size_t hlimit = 0, bool hwide = false) {
   __shared__ uint8_t nib[kOpeGroups * kOpeBlock];
   __shared__ uint32_t wsum[kOpeBlock / 64];
   const int tid = threadIdx.x;
@@ -726,22 +711,12 @@ __device__ __forceinline__ void ope_store_mask(uint32_t m, uint32_t* __restrict_
   if (hlimit == 0) {
     masks[wi] = word;
   } else if (hwide) {
-    // over PCIe: the tile's 1 KiB as wider stores (A/B: hwide 1 = 8-byte system-scope stores by the first
-    // two waves, 2 = 16-byte non-temporal stores by the first wave); the buffer is 16-byte aligned (the
-    // launcher checks), words past its end dropped
+    // over PCIe: the tile's 1 KiB as 16-byte non-temporal stores by the first wave; the buffer is 16-byte
+    // aligned (the launcher checks), words past its end dropped
     __shared__ __attribute__((aligned(16))) uint32_t wbuf[kOpeBlock];
     wbuf[tid] = word;
     __syncthreads();
-    if (hwide == 1) {
-      if (tid < kOpeBlock / 2) {
-        const size_t w0 = tile * kOpeBlock + 2 * (size_t)tid;
-        const uint64_t v = reinterpret_cast<const uint64_t*>(wbuf)[tid];
-        if (w0 + 1 < hlimit)
-          __hip_atomic_store(reinterpret_cast<uint64_t*>(masks + w0), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        else if (w0 < hlimit)
-          __hip_atomic_store(masks + w0, (uint32_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
-    } else if (tid < kOpeBlock / 4) {
+    if (tid < kOpeBlock / 4) {
       const size_t w0 = tile * kOpeBlock + 4 * (size_t)tid;
       const uint4 v = reinterpret_cast<const uint4*>(wbuf)[tid];
       if (w0 + 3 < hlimit) {
@@ -777,13 +752,14 @@ __device__ __forceinline__ void ope_store_mask(uint32_t m, uint32_t* __restrict_
 //                  writes the row ids; the last block writes the total.
 // total (nullable, zeroed by the caller): every tile also adds its count to it (one atomic per tile),
 // so the Search bitmask route has its match count without a reduction launch
+// (four waves per SIMD: the 32 rows a thread holds sit at the 128-VGPR boundary)
 template <bool HasValid>
-__global__ void __launch_bounds__(kOpeBlock) k_ope_count(const int64_t* __restrict__ col,
+__global__ void __launch_bounds__(kOpeBlock, 4) k_ope_count(const int64_t* __restrict__ col,
                                                          const uint8_t* __restrict__ valid, size_t n, int64_t bound,
                                                          int op, uint32_t vmask, uint32_t vbad,
                                                          uint32_t* __restrict__ masks, uint32_t* __restrict__ counts,
                                                          unsigned long long* __restrict__ total, size_t hlimit,
-                                                         int hwide) {
+                                                         bool hwide) {
   const bool vec = ((uintptr_t)col % 16 == 0) && (!HasValid || (uintptr_t)valid % 4 == 0);
   const uint32_t m = ope_thread_mask<HasValid>(col, valid, n, bound, op, blockIdx.x, vec, vmask, vbad);
   ope_store_mask(m, masks, counts, blockIdx.x, total, hlimit, hwide);
@@ -1055,18 +1031,11 @@ __global__ void __launch_bounds__(256) k_bigmul_carry(const uint32_t* __restrict
 // ------------------------------------------------------------------------------
 // 2048-bit moduli (RSA n) use S = 76, not the minimal 74: 4-limb blocks (fewer loop instructions per
 // CIOS step) and room for the QP modulus (no v_mul_lo) outweigh the 5.5 % more mads: MultAll fold
-// 4.08-4.11 -> 4.01 ms over 10M rows (profiles/r01_rsa76_ab.txt). DDSHE_RSA76=0 keeps S = 74.
-static bool use_rsa76() {
-  static const bool on = [] {
-    const char* e = getenv("DDSHE_RSA76");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
+// 4.08-4.11 -> 4.01 ms over 10M rows (profiles/r01_rsa76_ab.txt). No column has S = 74; k_fold1<74>
+// runs the 74-limb fold over a 76-limb column (fold1_limbs).
 Shape pick_shape(size_t mod_bits) {
   for (const Shape& s : kShapes) {
-    if (s.S == (use_rsa76() ? 74 : 76)) continue;
+    if (s.S == 74) continue;  // k_fold1's limb count over 76-limb columns, never a column's shape
     if ((size_t)s.W * s.S >= mod_bits + 2) return s;
   }
   return Shape{0, 0, 0};
@@ -1096,11 +1065,7 @@ hipError_t launch_egress_be(const uint32_t* X, size_t stride, size_t count, int 
 hipError_t launch_ingest_be(const uint8_t* in, size_t width, size_t count, int S, int W, const uint32_t* n2x,
                             uint32_t* X, size_t stride, uint32_t* flags, hipStream_t st, uint8_t* rowflags) {
   if (count == 0) return hipSuccess;
-  static const bool lds = [] {  // DDSHE_INGEST_LDS=0: per-thread row walk (A/B timing)
-    const char* e = getenv("DDSHE_INGEST_LDS");
-    return !(e && e[0] == '0');
-  }();
-  if (lds && width % 16 == 0 && width <= kIngestMaxW && (uintptr_t)in % 16 == 0) {
+  if (width % 16 == 0 && width <= kIngestMaxW && (uintptr_t)in % 16 == 0) {
     const size_t smem = (size_t)kIngestRows * (width / 4 + 1) * 4;
     hipLaunchKernelGGL(k_ingest_be_lds, dim3((unsigned)((count + kIngestRows - 1) / kIngestRows)),
                        dim3(kIngestThreads), smem, st, in, width, count, S, W, n2x, X, stride, flags, rowflags);
@@ -1121,9 +1086,8 @@ hipError_t launch_reduce_rows(int S, uint32_t* X, size_t stride, size_t count, c
 
 hipError_t launch_fold(int S, const uint32_t* X, size_t xstride, size_t count, const uint32_t* consts,
                        const uint32_t* qp_mod, uint32_t n0, uint32_t* P, size_t pstride, size_t ngroups, int s_out,
-                       hipStream_t st, const uint32_t* ids, int lane1, size_t inblock_pgs) {
+                       hipStream_t st, const uint32_t* ids, int lane1) {
   if (ngroups == 0 || ngroups > count) return hipErrorInvalidValue;
-  if (inblock_pgs) s_out = 0;  // the kernel zeroes the leaves' upper limbs itself
   if (lane1 && !(fold1_shape(S) && (lane1 == S || (S == 76 && lane1 == 74)))) return hipErrorInvalidValue;
   const int sw = lane1 ? lane1 : S;  // limbs the kernel writes
   // limbs sw..s_out of the partials (tail shape is wider): zero, contiguous in the limb-major layout
@@ -1161,15 +1125,6 @@ hipError_t launch_fold(int S, const uint32_t* X, size_t xstride, size_t count, c
     return hipGetLastError();
   }
   const uint32_t* c = qp_mod ? qp_mod : consts;  // N~ = N·n0 in place of N (Mont QP): no v_mul_lo per CIOS step
-  if (inblock_pgs) {  // one partial per block (k_fold InBlock), row-major leaves of inblock_pgs words
-    if (!qp_mod || ids || lane1) return hipErrorInvalidValue;
-    DDSHE_SWITCH(S, {
-      if (ngroups % (256 / TPI) != 0 || inblock_pgs < (size_t)S) return hipErrorInvalidValue;
-      hipLaunchKernelGGL((k_fold<S, TPI, W, true, false, false, true>), dim3(grid_for(ngroups * TPI)), dim3(256), 0,
-                         st, X, xstride, count, c, n0, P, 1, ngroups, nullptr, S, inblock_pgs);
-    });
-    return hipGetLastError();
-  }
   if (qp_mod && ids) {
     DDSHE_SWITCH(S, hipLaunchKernelGGL((k_fold<S, TPI, W, true, true>), dim3(grid_for(ngroups * TPI)), dim3(256), 0, st, X, xstride, count, c,
                                        n0, P, pstride, ngroups, ids));
@@ -1226,57 +1181,27 @@ hipError_t fold1_occupancy(int S, int* blocks_per_cu) {
   }
 }
 
-bool fold_qp_enabled() {  // DDSHE_FOLD_QP=0 disables (A/B timing)
-  static const bool on = [] {
-    const char* e = getenv("DDSHE_FOLD_QP");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // Latency-bound tree levels of the 4096-bit tail shape (S = 160, W = 28) run with 32 lanes per
 // bignum (L = 5 limbs per lane): a Montgomery step issues 10 mads per wave instead of 20, and
 // these levels have at most one wave per SIMD, so the step time is the issue time of one wave.
 // Levels with more groups stay at TPI = 16 (fewer exchange instructions per mad). Same limb
-// layout and constants for both, so levels mix freely. DDSHE_TAIL32=0 disables (A/B timing).
+// layout and constants for both, so levels mix freely.
 constexpr size_t kTail32MaxGroups = 2048;
-bool tail_qp(int S) {  // DDSHE_TAIL_QP=0 disables (A/B timing)
-  static const bool on = [] {
-    const char* e = getenv("DDSHE_TAIL_QP");
-    return !(e && e[0] == '0');
-  }();
-  return on && S == 160;
-}
-static bool use_tail32(int S, size_t ngroups) {
-  static const bool on = [] {
-    const char* e = getenv("DDSHE_TAIL32");
-    return !(e && e[0] == '0');
-  }();
-  return on && S == 160 && ngroups <= kTail32MaxGroups;
-}
+bool tail_qp(int S) { return S == 160; }
+static bool use_tail32(int S, size_t ngroups) { return S == 160 && ngroups <= kTail32MaxGroups; }
 
 // The widest tail levels of the 4096-bit shape (>= 8192 products: throughput-bound, 2+ waves per SIMD at
 // 8 lanes per bignum) run at TPI = 8: 40 mads per step against the same ~18 exchange/quotient
-// instructions as at TPI = 16 (20 mads). DDSHE_TAIL8=0 disables (A/B timing).
+// instructions as at TPI = 16 (20 mads).
 constexpr size_t kTail8MinGroups = 8192;
-static bool use_tail8(int S, size_t ngroups) {
-  static const bool on = [] {
-    const char* e = getenv("DDSHE_TAIL8");
-    return !(e && e[0] == '0');
-  }();
-  return on && S == 160 && ngroups >= kTail8MinGroups;
-}
+static bool use_tail8(int S, size_t ngroups) { return S == 160 && ngroups >= kTail8MinGroups; }
 
 // The 2048-bit tail shape (S = 80, 16 lanes per bignum) gets many more leaves since MultAll folds at one
 // bignum per lane (131,072 level-1 partials at 10M rows): its widest levels are throughput-bound and run
 // at 4 lanes per bignum (>= 32768 products: 40 mads per step against ~14 exchange/quotient instructions)
-// or 8 (>= 16384). DDSHE_TAIL80=0 disables (A/B timing).
+// or 8 (>= 16384).
 static int tail80_tpi(int S, size_t ngroups) {
-  static const bool on = [] {
-    const char* e = getenv("DDSHE_TAIL80");
-    return !(e && e[0] == '0');
-  }();
-  if (!on || S != 80) return 0;
+  if (S != 80) return 0;
   return ngroups >= 32768 ? 4 : ngroups >= 16384 ? 8 : 0;
 }
 
@@ -1359,17 +1284,6 @@ hipError_t launch_fold_tail(int S, const uint32_t* X, size_t xstride, size_t cou
   return hipGetLastError();
 }
 
-hipError_t launch_finalize_tail(int S, const uint32_t* P, size_t pstride, const uint32_t* consts, const uint32_t* Y,
-                                uint32_t n0, uint32_t* out, hipStream_t st) {
-  if (use_tail32(S, 1)) {
-    hipLaunchKernelGGL((k_finalize<160, 32, 28>), dim3(1), dim3(64), 0, st, P, pstride, consts, Y, n0, out);
-    return hipGetLastError();
-  }
-  DDSHE_TAIL_SWITCH(S, hipLaunchKernelGGL((k_finalize<S, TPI, W>), dim3(1), dim3(64), 0, st, P, pstride, consts, Y, n0,
-                                          out));
-  return hipGetLastError();
-}
-
 int tail_tpi() { return 16; }
 
 hipError_t launch_pairs(int S, const uint32_t* A, const uint32_t* B, size_t stride, size_t count,
@@ -1404,11 +1318,6 @@ hipError_t launch_modexp_pre(int S, const uint32_t* Xcol, size_t xstride, size_t
   return hipGetLastError();
 }
 
-#ifdef DDSHE_LADDER_OCC2
-constexpr int kLadderSlots = 2;
-#else
-constexpr int kLadderSlots = 1;
-#endif
 hipError_t launch_modexp_ladder(int S, const uint32_t* Tab, size_t tstride, const uint32_t* m, size_t count,
                                 const uint32_t* consts, const uint32_t* qp_mod, const uint32_t* gR,
                                 const uint32_t* sched, int nsched, uint32_t n0, uint32_t* O, size_t ostride,
@@ -1416,11 +1325,11 @@ hipError_t launch_modexp_ladder(int S, const uint32_t* Tab, size_t tstride, cons
   if (count == 0) return hipSuccess;
   if (qp_mod) {
     DDSHE_SWITCH(S, hipLaunchKernelGGL((k_modexp_ladder<S, TPI, W, true>), dim3(grid_for(count * TPI)), dim3(256),
-                                       (256 / TPI) * kLadderSlots * S * 4, st, Tab, tstride, m, count, consts, qp_mod, gR, sched,
+                                       (256 / TPI) * S * 4, st, Tab, tstride, m, count, consts, qp_mod, gR, sched,
                                        nsched, n0, O, ostride));
   } else {
     DDSHE_SWITCH(S, hipLaunchKernelGGL((k_modexp_ladder<S, TPI, W>), dim3(grid_for(count * TPI)), dim3(256),
-                                       (256 / TPI) * kLadderSlots * S * 4, st, Tab, tstride, m, count, consts, nullptr, gR, sched,
+                                       (256 / TPI) * S * 4, st, Tab, tstride, m, count, consts, nullptr, gR, sched,
                                        nsched, n0, O, ostride));
   }
   return hipGetLastError();
@@ -1540,17 +1449,11 @@ void ope_code(int64_t bound, int op, int64_t* t, int* code) {
 void ope_count(const int64_t* col, const uint8_t* valid, size_t n, int64_t bound, int op, uint32_t* masks,
                uint32_t* counts, hipStream_t st, uint32_t vmask, uint32_t vbad,
                unsigned long long* total = nullptr, size_t hlimit = 0) {
-  // zero-copy mask store width (DDSHE_MASK_STORE, A/B: 16 = 16-byte non-temporal stores by the tile's
-  // first wave (default: 0.0445-0.0457 ms per 10M-row Search route against 0.046-0.055 for one word per
-  // lane on the same box); 8 = 8-byte system-scope stores; 4 = one word per lane, system-scope; plain
+  // zero-copy mask stores: 16-byte non-temporal stores by the tile's first wave (0.0445-0.0457 ms per
+  // 10M-row Search route against 0.046-0.055 for one system-scope word per lane on the same box; plain
   // 16-byte stores were slower, 0.058 ms: the lines sit in L2 until the kernel's end-of-kernel write-back).
-  // The wider forms need a 16-byte aligned buffer, else one word per lane
-  static const int wide_mode = [] {
-    const char* e = getenv("DDSHE_MASK_STORE");
-    const int v = e ? atoi(e) : 16;
-    return v == 8 ? 1 : v == 16 ? 2 : 0;
-  }();
-  const int hwide = (hlimit && ((uintptr_t)masks & 15) == 0) ? wide_mode : 0;
+  // They need a 16-byte aligned buffer, else one word per lane
+  const bool hwide = hlimit && ((uintptr_t)masks & 15) == 0;
   const size_t nb = ope_blocks(n);
   int64_t t;
   int code;

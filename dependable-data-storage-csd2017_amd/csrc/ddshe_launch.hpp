@@ -45,9 +45,7 @@ hipError_t launch_fold(int S, const uint32_t* X, size_t xstride, size_t count, c
                        const uint32_t* qp_mod, uint32_t n0,
                        uint32_t* P, size_t pstride, size_t ngroups, int s_out, hipStream_t st,
                        const uint32_t* ids = nullptr,  // ids: fold rows ids[0..count) (device, u32)
-                       int lane1 = 0,  // != 0: one bignum per lane (k_fold1) at lane1 = fold1_limbs(S, bits) limbs
-                       size_t inblock_pgs = 0);  // != 0: k_fold InBlock, one row-major leaf of this many words per block
-bool fold_qp_enabled();
+                       int lane1 = 0);  // != 0: one bignum per lane (k_fold1) at lane1 = fold1_limbs(S, bits) limbs
 // Digit-form fold of a perfect-square modulus n² in the (148, 4, 28) shape (ddshe_foldsq.hpp): values as
 // two base-n digits of kFoldSqLimbs limbs each. sq: kSqCount vectors of kFoldSqLimbs limbs (ñ = k·n | n |
 // C | R mod n), k = -n⁻¹ mod 2^28. The mirror D and the digit partials Q are limb-major, 2·kFoldSqLimbs
@@ -71,7 +69,7 @@ bool fold1_shape(int S);
 int fold1_limbs(int S, size_t bits);
 size_t fold1_min_rows(int S, int cus);
 hipError_t fold1_occupancy(int S, int* blocks_per_cu);
-// tree levels / finalize in the tail shape (S = tail limb count, consts of the tail shape)
+// tree levels in the tail shape (S = tail limb count, consts of the tail shape)
 // qp_mod (nullable): N~ = N·n0 in tail limbs, used by the latency-bound levels when tail_qp(S)
 bool fold_narrow_shape(int S2);
 hipError_t launch_fold_narrow(int S2, const uint32_t* X, size_t xstride, size_t count, int sin, const uint32_t* consts,
@@ -97,8 +95,6 @@ hipError_t launch_tree(int S, const uint32_t* X, size_t xstride, int Sin, int Wi
 // results): one workgroup per pair (k_pairs_sos). consts as launch_tree, R2 = R^2 mod N (R = 2^(W S)).
 hipError_t launch_pairs_sos(int S, const uint32_t* A, const uint32_t* B, size_t n, const uint32_t* consts,
                             const uint32_t* R2, uint32_t* out, hipStream_t st);
-hipError_t launch_finalize_tail(int S, const uint32_t* P, size_t pstride, const uint32_t* consts, const uint32_t* Y,
-                                uint32_t n0, uint32_t* out, hipStream_t st);
 hipError_t launch_pairs(int S, const uint32_t* A, const uint32_t* B, size_t stride, size_t count,
                         const uint32_t* consts, uint32_t n0, uint32_t* O, hipStream_t st);
 // the same in a tail (latency) shape: S = tail limbs, consts of the tail shape (a few pairs per launch)

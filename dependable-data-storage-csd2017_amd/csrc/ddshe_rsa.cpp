@@ -70,7 +70,7 @@ int get_rsa_key(dds_ctx* ctx, const bn::Limbs& p_in, const bn::Limbs& q_in, std:
     const auto nb = be_of(k->n);
     if ((rc = get_mod(ctx, nb.data(), nb.size(), &k->mn))) return rc;
   }
-  k->plan = rsa_crt_plan(p, q, pick_sw, ladder1_enabled(), fold_qp_enabled());
+  k->plan = rsa_crt_plan(p, q, pick_sw, ladder1_enabled());
   const bool crt = k->plan.s1[0] >= 0;
   for (int i = 0; crt && i < 2; ++i) {
     const auto fb = be_of(k->f[i]);
@@ -251,7 +251,7 @@ int dds_rsa_crt_plan(dds_ctx* ctx, const uint8_t* p_be, size_t p_bytes, const ui
     int rc;
     if ((rc = check_factors(p, q))) return rc;
     if (!pick_shape(bn::bit_length(p) + bn::bit_length(q)).S) return fail(DDS_E_UNSUPPORTED, "modulus too large");
-    const RsaCrtPlan pl = rsa_crt_plan(p, q, pick_sw, ladder1_enabled(), fold_qp_enabled());
+    const RsaCrtPlan pl = rsa_crt_plan(p, q, pick_sw, ladder1_enabled());
     for (int i = 0; i < 2; ++i) {
       s1[i] = pl.s1[i];
       qp[i] = pl.qp[i];

@@ -63,17 +63,17 @@ struct RsaCrtPlan {
   size_t min_bits[2] = {0, 0};
 };
 
-// pick(bits) -> the lane-group shape of a modulus of that many bits; qp_lanes: whether lane-group shapes
-// use the QP modulus where it fits (fold_qp_enabled)
+// pick(bits) -> the lane-group shape of a modulus of that many bits (lane-group shapes use the QP modulus
+// where it fits)
 template <class Pick>
-inline RsaCrtPlan rsa_crt_plan(const bn::Limbs& p, const bn::Limbs& q, Pick pick, bool ladder1, bool qp_lanes) {
+inline RsaCrtPlan rsa_crt_plan(const bn::Limbs& p, const bn::Limbs& q, Pick pick, bool ladder1) {
   RsaCrtPlan pl;
   const bn::Limbs n = bn::mul(p, q);
   const ShapeSW sn = pick(bn::bit_length(n));
   const bn::Limbs* f[2] = {&p, &q};
   auto lanes_qp = [&](const bn::Limbs& N, const ShapeSW& sh) {
     const bn::Limbs nq = bn::mul(N, bn::Limbs{bn::mont_n0(N[0], sh.W)});
-    return qp_lanes && (size_t)sh.W * sh.S >= bn::bit_length(nq) + 2;
+    return (size_t)sh.W * sh.S >= bn::bit_length(nq) + 2;
   };
   auto full = [&]() {
     pl.s1[0] = pl.s1[1] = -1;

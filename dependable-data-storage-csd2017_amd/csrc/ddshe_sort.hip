@@ -176,13 +176,6 @@ __global__ void __launch_bounds__(1024) k_rs_red(const uint64_t* __restrict__ pa
   }
 }
 
-// the end of a call's device work: plan and overflow flag to host memory (one thread)
-__global__ void k_rs_publish(const uint32_t* __restrict__ ctl, const uint64_t* __restrict__ plan,
-                             uint64_t* __restrict__ hout) {
-  hout[2] = ctl[1];  // kMsdCtlOverflow
-  hout[3] = plan ? plan[1] : 0ull;
-}
-
 __global__ void k_rs_iota(uint32_t* __restrict__ ids, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) ids[i] = (uint32_t)i;
@@ -208,12 +201,11 @@ __device__ __forceinline__ uint32_t rs_digit(uint64_t k, uint32_t id, const uint
   return d;
 }
 
-// Tile of a block. xcd != 0: blocks are dealt round-robin over the 8 XCDs (observed; speed only, never
+// Tile of a block. Blocks are dealt round-robin over the 8 XCDs (observed; speed only, never
 // correctness), so block b works on tile (b % 8)-th eighth + b / 8: each XCD walks a contiguous range of
 // tiles and neighbouring tiles' writes to one digit run meet in the same L2.
-__device__ __forceinline__ size_t rs_tile(size_t nblocks, int xcd) {
+__device__ __forceinline__ size_t rs_tile(size_t nblocks) {
   const size_t b = blockIdx.x;
-  if (!xcd) return b;
   const size_t q = nblocks >> 3, r = nblocks & 7, x = b & 7;
   return x * q + (x < r ? x : r) + (b >> 3);
 }
@@ -241,7 +233,7 @@ __global__ void __launch_bounds__(HB) k_rs_hist(const uint64_t* __restrict__ key
                                                      uint32_t* __restrict__ hist, size_t nblocks,
                                                      uint32_t* __restrict__ clr, uint32_t nclr, bool pairs,
                                                      const uint32_t* __restrict__ khi,
-                                                     const uint64_t* __restrict__ plan, bool rowatom,
+                                                     const uint64_t* __restrict__ plan,
                                                      uint64_t* __restrict__ mm = nullptr) {
   if (plan) {  // speculative call: kmin and the shift (relative to s1) from k_rs_red's plan
     const uint64_t s1 = plan[1];
@@ -252,11 +244,11 @@ __global__ void __launch_bounds__(HB) k_rs_hist(const uint64_t* __restrict__ key
   constexpr size_t kRows = RsTile<BLK>::kRows;
   constexpr int kIt = (int)(kRows / HB);  // rows per thread
   constexpr int kW = HB / 64;
-  // rowatom: one LDS atomic per row into the wave's own copy of the counts (digits of a wave mostly
-  // distinct), else one per distinct digit of the wave found by 9 ballots (digits repeating)
+  // one LDS atomic per row into the wave's own copy of the counts (one atomic per distinct digit of a wave,
+  // found by 9 ballots, measured slower on the same box, 10M rows: raw call 0.318 -> 0.287 ms on the bench's
+  // OPE column, 0.675 -> 0.652 on uniform 54-bit keys, 0.265 -> 0.275 with every wave's digits equal)
   __shared__ uint32_t wcnt[kW][kRsDigits];
-  uint32_t* cnt = &wcnt[0][0];
-  for (int d = threadIdx.x; d < kW * kRsDigits; d += HB) cnt[d] = 0;
+  for (int d = threadIdx.x; d < kW * kRsDigits; d += HB) (&wcnt[0][0])[d] = 0;
   if (clr) {  // first pass of the MSD path: the bucket tables of the last scatter start at their identities
     const size_t g = (size_t)blockIdx.x * HB + threadIdx.x;
     for (size_t g2 = g; g2 < nclr; g2 += (size_t)gridDim.x * HB)
@@ -264,7 +256,6 @@ __global__ void __launch_bounds__(HB) k_rs_hist(const uint64_t* __restrict__ key
   }
   __syncthreads();
   const int lane = threadIdx.x & 63;
-  const uint64_t lt = (1ull << lane) - 1ull;
   const bool need_id = last && valid && !kbit;
   // all loads first (independent, in flight together), then the LDS counting
   uint64_t key[kIt];
@@ -337,27 +328,11 @@ __global__ void __launch_bounds__(HB) k_rs_hist(const uint64_t* __restrict__ key
       atomicMax(reinterpret_cast<unsigned long long*>(mm) + (blockIdx.x % kCarryWords), (unsigned long long)v);
     }
   }
-  if (rowatom) {
-    uint32_t* mine = &wcnt[threadIdx.x >> 6][0];
+  uint32_t* mine = &wcnt[threadIdx.x >> 6][0];
 #pragma unroll
-    for (int k = 0; k < kIt; ++k) {
-      const size_t i = rix[k];
-      if (i < n) atomicAdd(&mine[rs_digit(key[k], id[k], valid, shift, last, desc, vbit, kbit)], 1u);
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < kIt; ++k) {
-      const size_t i = rix[k];
-      const uint32_t d = i < n ? rs_digit(key[k], id[k], valid, shift, last, desc, vbit, kbit) : kRsNone;
-      // one LDS atomic per distinct digit of the wave
-      uint64_t peers = ~0ull;
-#pragma unroll
-      for (int b = 0; b < 9; ++b) {
-        const uint64_t bal = __ballot((d >> b) & 1u);
-        peers &= ((d >> b) & 1u) ? bal : ~bal;
-      }
-      if (d != kRsNone && (peers & lt) == 0) atomicAdd(&cnt[d], (uint32_t)__popcll(peers));
-    }
+  for (int k = 0; k < kIt; ++k) {
+    const size_t i = rix[k];
+    if (i < n) atomicAdd(&mine[rs_digit(key[k], id[k], valid, shift, last, desc, vbit, kbit)], 1u);
   }
   __syncthreads();
   for (int d = threadIdx.x; d < kRsDigits; d += HB) {  // 1 KiB, coalesced
@@ -482,7 +457,7 @@ __global__ void __launch_bounds__(BLK) k_rs_scatter(const uint64_t* __restrict__
                                                          const uint32_t* __restrict__ ctot,
                                                          const uint32_t* __restrict__ dtot, size_t nblocks,
                                                          uint64_t* __restrict__ keys_out,
-                                                         uint32_t* __restrict__ ids_out, int xcd, MsdRuns runs,
+                                                         uint32_t* __restrict__ ids_out, MsdRuns runs,
                                                          const uint32_t* __restrict__ khi,
                                                          uint32_t* __restrict__ khi_out,
                                                          const uint64_t* __restrict__ plan) {
@@ -493,7 +468,7 @@ __global__ void __launch_bounds__(BLK) k_rs_scatter(const uint64_t* __restrict__
     shift += (int)s1;
     runs.s1 = (int)s1;
   }
-  const size_t tile = rs_tile(nblocks, xcd);
+  const size_t tile = rs_tile(nblocks);
   using T = RsTile<BLK>;
   constexpr int W = T::kWaves;
   __shared__ uint32_t cnt[W][kRsDigits];
@@ -730,19 +705,19 @@ __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
 constexpr int kPartRows = 16;  // rows per lane in flight (8: the same kernel time within noise)
 constexpr int kMsdBlkThreads = 256;  // k_msd_local_blk: a block per bucket,
 constexpr int kMsdBlkRows = 16;       // kMsdBlkRows rows per lane: up to 4,096 rows from registers
-// fuse: the bucket's ids are still only in ids[] (not copied to src yet): round 0 reads them there and
+// The bucket's ids are still only in ids[] (not copied to src yet): round 0 reads them there and
 // writes the copy to src as it goes. Its compacted writes land at positions it has already read (out never
 // passes the rows loaded so far), and later rounds read src.
 __device__ __forceinline__ bool msd_wave_partition(const uint64_t* __restrict__ keys, uint32_t* __restrict__ src,
                                                    uint32_t* __restrict__ ids, uint32_t lo, uint32_t m, int lane,
-                                                   int max_rounds, bool fuse = false) {
+                                                   int max_rounds) {
   const uint64_t lt = (1ull << lane) - 1ull;
   uint64_t cur = keys[lo];
   uint32_t out = lo;
   bool restarted = false;
   for (int round = 0; round < max_rounds; ++round) {
     uint64_t nxt = ~0ull, below = ~0ull;
-    const bool copy = fuse && round == 0;
+    const bool copy = round == 0;
     for (uint32_t p0 = 0; p0 < m; p0 += 64 * kPartRows) {
       uint64_t k[kPartRows];
       uint32_t id[kPartRows];
@@ -795,12 +770,12 @@ __device__ __forceinline__ bool msd_wave_partition(const uint64_t* __restrict__ 
 // buckets: 2 keys ~1,900 rows, 3 keys ~2,900, up to ~3,950 with 4). Rows past m read as key ~0: they never
 // lower the minimum or the next key, and as hits of a round whose key is ~0 (a real key only at a full
 // 64-bit span) they sit in the last positions, after every real row: their stores past the bucket are
-// dropped. fuse: ids[] is overwritten only after every wave holds its rows (a barrier); the side copy
+// dropped. ids[] is overwritten only after every wave holds its rows (a barrier); the side copy
 // src[] is written only if the rounds run out (k_msd_big reads it).
 template <int E, int NW>
 __device__ __forceinline__ bool msd_block_partition(const uint64_t* __restrict__ keys, uint32_t* __restrict__ src,
                                                     uint32_t* __restrict__ ids, uint32_t lo, uint32_t m,
-                                                    int max_rounds, bool fuse, uint32_t (*scnt)[NW],
+                                                    int max_rounds, uint32_t (*scnt)[NW],
                                                     uint64_t (*smin)[NW]) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const uint64_t lt = (1ull << lane) - 1ull;
@@ -811,7 +786,7 @@ __device__ __forceinline__ bool msd_block_partition(const uint64_t* __restrict__
   for (int r = 0; r < E; ++r) {
     const uint32_t pos = min(w0 + (uint32_t)(r * 64 + lane), m - 1);
     k[r] = keys[lo + pos];
-    id[r] = fuse ? ids[lo + pos] : src[lo + pos];
+    id[r] = ids[lo + pos];
   }
   uint64_t below = ~0ull;
 #pragma unroll
@@ -862,12 +837,10 @@ __device__ __forceinline__ bool msd_block_partition(const uint64_t* __restrict__
     if (out >= end) return true;  // block-uniform
     cur = nb;
   }
-  if (fuse) {
 #pragma unroll
-    for (int r = 0; r < E; ++r) {
-      const uint32_t pos = w0 + (uint32_t)(r * 64 + lane);
-      if (pos < m) src[lo + pos] = id[r];
-    }
+  for (int r = 0; r < E; ++r) {
+    const uint32_t pos = w0 + (uint32_t)(r * 64 + lane);
+    if (pos < m) src[lo + pos] = id[r];
   }
   return false;
 }
@@ -891,41 +864,14 @@ __device__ __forceinline__ void msd_wave_sort(const uint64_t* __restrict__ keys,
   }
 }
 
-// One wave's work on multi-key bucket b (rows [lo, lo + m)): copy its ids (and, gather mode, its keys)
-// to the side buffers, then the stable partition, or the in-register network, or the big-bucket list.
-__device__ __forceinline__ void msd_bucket(const int64_t* __restrict__ col, int desc, uint64_t kmin,
-                                           uint64_t* __restrict__ keys, uint32_t* __restrict__ src,
+// One wave's work on multi-key bucket b (rows [lo, lo + m)), its keys as the last pass wrote them: the
+// stable partition (whose first round copies the bucket's ids to the side buffer, free after the last
+// pass), or the in-register network, or the big-bucket list.
+__device__ __forceinline__ void msd_bucket(const uint64_t* __restrict__ keys, uint32_t* __restrict__ src,
                                            uint32_t* __restrict__ ids, uint32_t b, uint32_t lo, uint32_t m, int s1,
-                                           uint32_t* __restrict__ ctl, uint32_t* __restrict__ big, int lane,
-                                           bool fuse_copy) {
-  // this bucket's grouped ids to the side buffer (free after the last pass), and (gather mode) their keys
-  // gathered from the column by id, read from there below; with the sorted keys written by the last pass
-  // the copy rides on the first partition round instead (DDSHE_ORDER_FUSECOPY=0: this loop, A/B)
-  const bool fuse = col == nullptr && fuse_copy;
-  for (uint32_t p0 = 0; p0 < (fuse ? 0u : m); p0 += 512) {  // 8 loads in flight per lane, then their stores
-    uint32_t v[8];
-    int64_t c[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const uint32_t p = p0 + (uint32_t)(r * 64 + lane);
-      v[r] = ids[lo + min(p, m - 1)];
-    }
-    if (col) {
-#pragma unroll
-      for (int r = 0; r < 8; ++r) c[r] = col[v[r]];
-    }
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const uint32_t p = p0 + (uint32_t)(r * 64 + lane);
-      if (p < m) {
-        src[lo + p] = v[r];
-        if (col) keys[lo + p] = rs_ukey((uint64_t)c[r], desc) - kmin;
-      }
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the wave's copies land before its lanes read them
+                                           uint32_t* __restrict__ ctl, uint32_t* __restrict__ big, int lane) {
   const int rounds = m <= kMsdWaveMax ? 2 : 16;
-  const bool done = msd_wave_partition(keys, src, ids, lo, m, lane, rounds, fuse);
+  const bool done = msd_wave_partition(keys, src, ids, lo, m, lane, rounds);
   if (done) return;
   if (m > kMsdWaveMax) {
     if (lane == 0) big[atomicAdd(&ctl[kMsdCtlBig], 1u)] = b;
@@ -938,17 +884,9 @@ __device__ __forceinline__ void msd_bucket(const int64_t* __restrict__ col, int 
   else msd_wave_sort<8, 9>(keys, src, ids, lo, m, rmask, lane);
 }
 
-// Bucket ranges (DDSHE_ORDER_MSDLIST=0, round 6's A/B path): one wave per `per_wave` consecutive buckets:
-// the wave's first lanes read their buckets' table entries
-// together, a ballot marks the buckets holding two distinct keys, and the wave orders those one after
-// another (bucket bounds made wave-uniform, so its addressing stays scalar). Round 5 ran one wave per
-// bucket: 65,536 waves, most reading one word and exiting. Same box, k_msd_local per 10M-row call on the
-// bench's OPE column (profiles/r06_msdwave_ab.txt): 1 bucket per wave 42.8 us, 2: 39.9, 4: 45.0, 8: ~51
-// (neighbouring multi-key buckets serialise); uniform 54-bit keys (every bucket multi-key): call 0.709 ->
-// 0.683 ms at 2.
-// (per_wave: DDSHE_ORDER_MSDWAVE, 2 by default; 1 is round 5's one wave per bucket, A/B; a power of 2 <= 64)
-// Lists (DDSHE_ORDER_MSDLIST=1, default; same box, profiles/r06_msdlist_ab.txt: raw call 0.270 -> 0.257 ms
-// on the bench column, uniform 54-bit keys within 1 %): k_msd_list first gathers the multi-key buckets, block i of 64
+// One wave per bucket range (round 5: 65,536 waves, most reading one word and exiting; round 6: ranges of 2
+// buckets) lost to lists (same box, profiles/r06_msdwave_ab.txt, profiles/r06_msdlist_ab.txt: raw call
+// 0.270 -> 0.257 ms on the bench column, uniform 54-bit keys within 1 %): k_msd_list first gathers the multi-key buckets, block i of 64
 // (1024 threads, one per bucket) writing its buckets of <= kMsdWaveMax rows to the front of list[1024 i ..
 // 1024 i + 1024), the larger ones to the back, and the two counts to count[i] / count[64 + i] (no atomics:
 // one atomic counter serialised 1,024 waves, 7.4 us). Then k_msd_local's waves take the small entries
@@ -956,7 +894,7 @@ __device__ __forceinline__ void msd_bucket(const int64_t* __restrict__ col, int 
 // k_msd_local_blk's blocks the large ones, one 256-thread block per bucket partitioning from registers up
 // to 4,096 rows (msd_block_partition; wave 0 on the memory rounds above that). The bench column's ~600
 // multi-key buckets of ~1,900 (2 keys) to ~3,950 rows (4 keys) then run one per block instead of one per
-// wave on the memory rounds, queued behind the 65,536 / per_wave bucket ranges, most of which find nothing.
+// wave on the memory rounds.
 constexpr int kMsdListBlocks = 64;
 constexpr int kMsdSmallBlocks = 1024;  // small list: 4,096 waves
 constexpr int kMsdLargeBlocks = 768;   // large list: 3 blocks per CU, one bucket each at a time
@@ -1017,86 +955,64 @@ struct MsdListView {
   }
 };
 
-__global__ void __launch_bounds__(256) k_msd_local(const int64_t* __restrict__ col, int desc, uint64_t kmin,
-                                                   uint64_t* __restrict__ keys, uint32_t* __restrict__ src,
+// the small entries of k_msd_list, one wave per bucket
+__global__ void __launch_bounds__(256) k_msd_local(const uint64_t* __restrict__ keys, uint32_t* __restrict__ src,
                                                    uint32_t* __restrict__ ids, MsdRuns runs,
                                                    uint32_t* __restrict__ ctl, uint32_t* __restrict__ big,
-                                                   const uint64_t* __restrict__ plan, uint32_t per_wave,
-                                                   bool fuse_copy, const uint32_t* __restrict__ list = nullptr) {
+                                                   const uint64_t* __restrict__ plan,
+                                                   const uint32_t* __restrict__ list) {
   if (plan) {
     const uint64_t s1 = plan[1];
     if (s1 == kRsNoPlan) return;
-    kmin = plan[0];
     runs.s1 = (int)s1;
   }
   const int lane = threadIdx.x & 63;
-  if (list) {  // the small entries of k_msd_list
-    const MsdListView lv(list, false, lane);
-    const uint32_t step = gridDim.x * 4;
-    uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    uint4 e = q < lv.n ? lv.entry(q) : make_uint4(0, 0, 0, 0);
-    while (q < lv.n) {  // the next entry's load in flight behind this bucket's work
-      const uint32_t qn = q + step;
-      const uint4 en = qn < lv.n ? lv.entry(qn) : make_uint4(0, 0, 0, 0);
-      const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.x);
-      const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y);
-      const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.z);
-      msd_bucket(col, desc, kmin, keys, src, ids, b, lo, m, runs.s1, ctl, big, lane, fuse_copy);
-      e = en;
-      q = qn;
-    }
-    return;
-  }
-  const uint32_t b0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * per_wave;
-  const uint32_t bl = b0 + ((uint32_t)lane & (per_wave - 1));
-  const uint32_t lo_l = runs.first[bl];
-  const bool need = lane < (int)per_wave && lo_l != ~0u &&
-                    (runs.multi[bl] != 0u || runs.kmin[bl] != runs.kmax[bl]);
-  const uint32_t m_l = need ? runs.end[bl] - lo_l : 0u;
-  uint64_t mask = __ballot(need);
-  while (mask) {
-    const int j = __builtin_ctzll(mask);
-    mask &= mask - 1ull;
-    // wave-uniform (SGPRs): the bucket's addressing stays scalar in msd_bucket
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)lo_l, j));
-    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane(__shfl((int)m_l, j));
-    msd_bucket(col, desc, kmin, keys, src, ids, b0 + (uint32_t)j, lo, m, runs.s1, ctl, big, lane, fuse_copy);
+  const MsdListView lv(list, false, lane);
+  const uint32_t step = gridDim.x * 4;
+  uint32_t q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  uint4 e = q < lv.n ? lv.entry(q) : make_uint4(0, 0, 0, 0);
+  while (q < lv.n) {  // the next entry's load in flight behind this bucket's work
+    const uint32_t qn = q + step;
+    const uint4 en = qn < lv.n ? lv.entry(qn) : make_uint4(0, 0, 0, 0);
+    const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.x);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y);
+    const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.z);
+    msd_bucket(keys, src, ids, b, lo, m, runs.s1, ctl, big, lane);
+    e = en;
+    q = qn;
   }
 }
 
 // the large entries of k_msd_list (> kMsdWaveMax rows), one block per bucket: the register partition up to
-// 256 x kMsdBlkRows rows with the fused side copy (the default); above that, or with the copy loop (gather
-// mode, DDSHE_ORDER_FUSECOPY=0), wave 0 alone as k_msd_local would; a bucket whose 16 rounds run out goes
-// to k_msd_big's list
-__global__ void __launch_bounds__(kMsdBlkThreads) k_msd_local_blk(const int64_t* __restrict__ col, int desc, uint64_t kmin,
-                                                       uint64_t* __restrict__ keys, uint32_t* __restrict__ src,
+// 256 x kMsdBlkRows rows with the fused side copy; above that, wave 0 alone as k_msd_local would; a bucket
+// whose 16 rounds run out goes to k_msd_big's list
+__global__ void __launch_bounds__(kMsdBlkThreads) k_msd_local_blk(const uint64_t* __restrict__ keys,
+                                                       uint32_t* __restrict__ src,
                                                        uint32_t* __restrict__ ids, MsdRuns runs,
                                                        uint32_t* __restrict__ ctl, uint32_t* __restrict__ big,
-                                                       const uint64_t* __restrict__ plan, bool fuse_copy,
+                                                       const uint64_t* __restrict__ plan,
                                                        const uint32_t* __restrict__ list) {
   if (plan) {
     const uint64_t s1 = plan[1];
     if (s1 == kRsNoPlan) return;
-    kmin = plan[0];
     runs.s1 = (int)s1;
   }
   constexpr int NW = kMsdBlkThreads / 64;
   __shared__ uint32_t scnt[2][NW];
   __shared__ uint64_t smin[2][NW];
   const int lane = threadIdx.x & 63;
-  const bool fuse = col == nullptr && fuse_copy;
   const MsdListView lv(list, true, lane);  // every wave of the block: the same entries
   for (uint32_t q = blockIdx.x; q < lv.n; q += gridDim.x) {
     const uint4 e = lv.entry(q);
     const uint32_t b = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.x);
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y);
     const uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)e.z);
-    if (fuse && m <= (uint32_t)kMsdBlkThreads * kMsdBlkRows) {
-      if (!msd_block_partition<kMsdBlkRows, NW>(keys, src, ids, lo, m, 16, true, scnt, smin) && threadIdx.x == 0)
+    if (m <= (uint32_t)kMsdBlkThreads * kMsdBlkRows) {
+      if (!msd_block_partition<kMsdBlkRows, NW>(keys, src, ids, lo, m, 16, scnt, smin) && threadIdx.x == 0)
         big[atomicAdd(&ctl[kMsdCtlBig], 1u)] = b;
       __syncthreads();  // scnt / smin free for the next bucket
     } else if (threadIdx.x < 64) {
-      msd_bucket(col, desc, kmin, keys, src, ids, b, lo, m, runs.s1, ctl, big, lane, fuse_copy);
+      msd_bucket(keys, src, ids, b, lo, m, runs.s1, ctl, big, lane);
     }
   }
 }
@@ -1123,8 +1039,8 @@ __device__ __forceinline__ void msd_block_sort(const uint64_t* __restrict__ keys
 // buckets of 513..8192 rows with more distinct keys than k_msd_local's partition rounds: one
 // workgroup each (grid-stride over the list); larger ones: overflow flag (host falls back to LSD)
 // hout (nullable): the call's read-back words (overflow flag, plan) stored to the host-mapped words by the
-// last block to finish (a ticket in ctl, cleared with the table by the call's first histogram), instead
-// of a k_rs_publish launch after it (DDSHE_ORDER_PUBLISH=1, A/B). kMsdBigBlocks < 2^16 (ticket bits).
+// last block to finish (a ticket in ctl, cleared with the table by the call's first histogram): no
+// one-thread launch after it. kMsdBigBlocks < 2^16 (ticket bits).
 __global__ void __launch_bounds__(1024) k_msd_big(const uint64_t* __restrict__ keys, const uint32_t* __restrict__ src,
                                                   uint32_t* __restrict__ ids, MsdRuns runs, uint32_t* __restrict__ ctl,
                                                   const uint32_t* __restrict__ big, const uint64_t* __restrict__ plan,
@@ -1184,25 +1100,7 @@ size_t rs_scratch_bytes(size_t n) {
 }
 
 // the MSD path pays off from 4 LSD passes on (a span of > 24 bits) and enough rows to fill the buckets
-static bool msd_enabled(size_t n, int sb) {
-  static const int mode = [] {
-    const char* s = getenv("DDSHE_ORDER_MSD");  // 0: LSD passes only (A/B)
-    return s ? atoi(s) : 1;
-  }();
-  return mode != 0 && n >= ((size_t)1 << 16) && sb > 24;
-}
-
-static int order_env(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
-static int order_xcd() {
-  static const int mode = [] {
-    const char* s = getenv("DDSHE_ORDER_XCD");  // 0: tile = block (A/B)
-    return s ? atoi(s) : 1;
-  }();
-  return mode;
-}
+static bool msd_enabled(size_t n, int sb) { return n >= ((size_t)1 << 16) && sb > 24; }
 
 // one LSD pass: per-tile digit counts, their scan over tiles, the stable scatter (tiles of BLK x kRsItems
 // rows; 256 threads measured fastest: 512 / 1024-thread tiles lengthen the write-out's digit runs but
@@ -1225,22 +1123,16 @@ static void rs_pass(hipStream_t st, const uint64_t* kin, const uint32_t* ids_in,
                     const CarryPass& cp = CarryPass{}) {
   const size_t nb = (n + RsTile<BLK>::kRows - 1) / RsTile<BLK>::kRows;
   // 16-byte key pairs for the counts: aligned keys (and valid bytes when the first pass reads them), no
-  // id read (DDSHE_ORDER_HPAIR=0: one row per lane, A/B)
-  static const int hpair = order_env("DDSHE_ORDER_HPAIR", 1);
-  const bool pairs = hpair && ((uintptr_t)kin & 15) == 0 && (ids_in || !valid || ((uintptr_t)valid & 1) == 0) &&
+  // id read; else one row per lane
+  const bool pairs = ((uintptr_t)kin & 15) == 0 && (ids_in || !valid || ((uintptr_t)valid & 1) == 0) &&
                      !(last && valid && !kbit);
-  // digit counts by per-row LDS atomics into per-wave copies (DDSHE_ORDER_HATOM=0: one atomic per distinct
-  // digit of a wave, found by 9 ballots, A/B): same box, 10M rows, raw call 0.318 -> 0.287 ms on the bench's
-  // OPE column, 0.675 -> 0.652 on uniform 54-bit keys, 0.265 -> 0.275 with every wave's digits equal
-  static const int hatom = order_env("DDSHE_ORDER_HATOM", 1);
   if (cp.mm) {  // carried plan: checked by k_rs_scan_chunks, before the scatter reads it
     hipLaunchKernelGGL((k_rs_hist<BLK, BLK>), dim3((unsigned)nb), dim3(BLK), 0, st, kin, ids_in, valid, n,
                        shift + cp.s1, last, desc, vbit, kbit, cp.kmin, hist, nb, clr, clr ? kMsdTableWords : 0u,
-                       pairs && !khi, khi, nullptr, hatom != 0, cp.mm);
+                       pairs && !khi, khi, nullptr, cp.mm);
   } else {
     hipLaunchKernelGGL((k_rs_hist<BLK, BLK>), dim3((unsigned)nb), dim3(BLK), 0, st, kin, ids_in, valid, n, shift, last,
-                       desc, vbit, kbit, kmin, hist, nb, clr, clr ? kMsdTableWords : 0u, pairs && !khi, khi, plan,
-                       hatom != 0);
+                       desc, vbit, kbit, kmin, hist, nb, clr, clr ? kMsdTableWords : 0u, pairs && !khi, khi, plan);
   }
   const size_t nch = (nb + kScanTiles - 1) / kScanTiles;
   hipLaunchKernelGGL(k_rs_scan_tiles, dim3((unsigned)nch), dim3(kScanThreads), 0, st, hist, nb, ctot);
@@ -1251,7 +1143,7 @@ static void rs_pass(hipStream_t st, const uint64_t* kin, const uint32_t* ids_in,
     hipLaunchKernelGGL(k_rs_scan_chunks, dim3(1), dim3(kScanThreads), 0, st, ctot, nch, dtot, nullptr, nullptr, 0ull,
                        -1);
   hipLaunchKernelGGL(k_rs_scatter<BLK>, dim3((unsigned)nb), dim3(BLK), 0, st, kin, ids_in, valid, n, shift, desc, vbit,
-                     kbit, last, kmin, hist, ctot, dtot, nb, kout, ids_out, order_xcd(), runs, khi, khi_out, plan);
+                     kbit, last, kmin, hist, ctot, dtot, nb, kout, ids_out, runs, khi, khi_out, plan);
 }
 
 // Spans of kSpecLo..kSpecHi bits take the MSD path with split keys and (with a valid array) the key-bit
@@ -1267,7 +1159,6 @@ static std::atomic<int> g_order_spec{0};
 // before the first scatter, and a plan that no longer fits (keys below kmin, or a span of another bit
 // length) makes every later kernel return; the call then runs the min / max pass and goes on as a call
 // without a carried plan. Shared by every caller (a race only costs a failed check).
-// DDSHE_ORDER_CARRY=0: the min / max pass every call (A/B).
 struct CarriedPlan {
   uint64_t kmin;
   int s1;   // -1: none
@@ -1311,14 +1202,11 @@ hipError_t launch_ope_order(const int64_t* col, const uint8_t* valid, size_t n, 
   uint32_t* mbig = mctl + 8;
   uint32_t* mlist = mbig + kMsdBuckets;  // k_msd_list's counts, then its multi-key buckets (kMsdListWords)
   hipError_t e = hipSuccess;
-  // the last pass writes the sorted keys too (DDSHE_ORDER_KEYS2=0: k_msd_local gathers its buckets' keys
-  // from the column by id instead: 80 MB less written, but k_msd_local 42 -> 59 us against scatter 76 -> 66)
-  static const int keys2 = order_env("DDSHE_ORDER_KEYS2", 1);
-  // the MSD path's first pass writes its keys as high and low 32-bit words in two arrays (the first n
-  // words of ka: low, the next n: high) when the last pass's digit and the validity bit are in the high
-  // words (span >= 2^40): the last histogram then reads 4 B per row (DDSHE_ORDER_SPLIT=0: 8 B, A/B)
-  static const int split_env = order_env("DDSHE_ORDER_SPLIT", 1);
-  static const int spec_env = order_env("DDSHE_ORDER_SPEC", 1);  // 0: bounds always read back first (A/B)
+  // The last pass of the MSD path writes the sorted keys too (k_msd_local reads its buckets' keys from
+  // there; gathering them from the column by id wrote 80 MB less but was slower: k_msd_local 42 -> 59 us
+  // against scatter 76 -> 66). Its first pass writes its keys as high and low 32-bit words in two arrays
+  // (the first n words of ka: low, the next n: high) when the last pass's digit and the validity bit are
+  // in the high words (span >= 2^40): the last histogram then reads 4 B per row.
   // executed pass j writes ids to fin when (np-1-j) is even, so the last one lands there; with msd.first
   // set the first pass clears the bucket table and the last fills it. plan: shifts relative to s1, kmin
   // and s1 from the device
@@ -1334,7 +1222,7 @@ hipError_t launch_ope_order(const int64_t* col, const uint8_t* valid, size_t n, 
       uint32_t* ids_out = ((np - 1 - j) % 2 == 0) ? fin : tmp;
       const bool last = j == np - 1;
       rs_pass<256>(st, kin, ids_in, valid, n, shifts[j], last, desc, vbit, kbit, kmin, hist, ctot, dtot,
-                   last ? (msd.first && keys2 ? kout : nullptr) : kout, ids_out, j == 0 ? msd.first : nullptr,
+                   (last && !msd.first) ? nullptr : kout, ids_out, j == 0 ? msd.first : nullptr,
                    last ? msd : none, j == 1 ? hi : nullptr, j == 0 ? hi : nullptr, plan,
                    j == 0 ? cp : CarryPass{});
       kin = kout;
@@ -1342,31 +1230,18 @@ hipError_t launch_ope_order(const int64_t* col, const uint8_t* valid, size_t n, 
       ids_in = ids_out;
     }
   };
-  static const int publish_env = order_env("DDSHE_ORDER_PUBLISH", 0);  // 1: k_rs_publish launch (A/B)
-  auto msd_tail = [&](uint64_t kmin, const uint64_t* plan) {
-    static const int fuse_copy = order_env("DDSHE_ORDER_FUSECOPY", 1);
-    static const uint32_t per_wave = [] {
-      const int v = order_env("DDSHE_ORDER_MSDWAVE", 2);
-      return (v >= 1 && v <= 64 && (v & (v - 1)) == 0) ? (uint32_t)v : 2u;
-    }();
-    static const int list_env = order_env("DDSHE_ORDER_MSDLIST", 1);  // 0: bucket ranges per wave (A/B)
-    if (list_env) {
-      hipLaunchKernelGGL(k_msd_list, dim3(kMsdListBlocks), dim3(1024), 0, st, runs, mlist, plan);
-      hipLaunchKernelGGL(k_msd_local, dim3(kMsdSmallBlocks), dim3(256), 0, st, keys2 ? nullptr : col, desc, kmin, kb,
-                         ib, out_ids, runs, mctl, mbig, plan, per_wave, fuse_copy != 0, mlist);
-      hipLaunchKernelGGL(k_msd_local_blk, dim3(kMsdLargeBlocks), dim3(kMsdBlkThreads), 0, st, keys2 ? nullptr : col, desc, kmin,
-                         kb, ib, out_ids, runs, mctl, mbig, plan, fuse_copy != 0, mlist);
-    } else {
-      hipLaunchKernelGGL(k_msd_local, dim3(kMsdBuckets / (4 * per_wave)), dim3(256), 0, st, keys2 ? nullptr : col,
-                         desc, kmin, kb, ib, out_ids, runs, mctl, mbig, plan, per_wave, fuse_copy != 0, nullptr);
-    }
+  auto msd_tail = [&](const uint64_t* plan) {
+    hipLaunchKernelGGL(k_msd_list, dim3(kMsdListBlocks), dim3(1024), 0, st, runs, mlist, plan);
+    hipLaunchKernelGGL(k_msd_local, dim3(kMsdSmallBlocks), dim3(256), 0, st, kb, ib, out_ids, runs, mctl, mbig, plan,
+                       mlist);
+    hipLaunchKernelGGL(k_msd_local_blk, dim3(kMsdLargeBlocks), dim3(kMsdBlkThreads), 0, st, kb, ib, out_ids, runs, mctl,
+                       mbig, plan, mlist);
     hipLaunchKernelGGL(k_msd_big, dim3(kMsdBigBlocks), dim3(1024), 0, st, kb, ib, out_ids, runs, mctl, mbig, plan,
-                       (hw && !publish_env) ? hw->d : nullptr);
+                       hw ? hw->d : nullptr);
   };
   // words 2..3 of hw after the call's device work: overflow flag, plan
-  auto read_ctl = [&](const uint64_t* plan, uint64_t* ovf, uint64_t* pl) -> hipError_t {
+  auto read_ctl = [&](uint64_t* ovf, uint64_t* pl) -> hipError_t {
     if (hw) {
-      if (publish_env) hipLaunchKernelGGL(k_rs_publish, dim3(1), dim3(1), 0, st, mctl, plan, hw->d);
       hipError_t r = hipStreamSynchronize(st);
       *ovf = hw->h[2];
       *pl = hw->h[3];
@@ -1385,10 +1260,9 @@ hipError_t launch_ope_order(const int64_t* col, const uint8_t* valid, size_t n, 
     hred[0] = ubounds[0] <= ubounds[1] ? (desc ? ~ubounds[1] : ubounds[0]) : 1;
     hred[1] = ubounds[0] <= ubounds[1] ? (desc ? ~ubounds[0] : ubounds[1]) : 0;
   } else {
-    static const int carry_env = order_env("DDSHE_ORDER_CARRY", 1);
     const CarriedPlan cpl = carry_get();
     bool carried = false;  // a carried plan ran and did not stand: the bounds come from the min / max pass now
-    if (hw && carry_env && spec_env && split_env && msd_enabled(n, kSpecLo) && cpl.s1 >= 0 && cpl.desc == desc) {
+    if (hw && msd_enabled(n, kSpecLo) && cpl.s1 >= 0 && cpl.desc == desc) {
       const uint64_t* plan = red + 2;
       CarryPass cp;
       cp.mm = cword;
@@ -1397,15 +1271,15 @@ hipError_t launch_ope_order(const int64_t* col, const uint8_t* valid, size_t n, 
       cp.s1 = cpl.s1;
       const int rel[2] = {0, 8};
       run_passes(rel, 2, out_ids, ib, runs, true, valid != nullptr, false, 0, plan, cp);
-      msd_tail(0, plan);
+      msd_tail(plan);
       uint64_t ovf = 0, pl = 0;
-      if ((e = read_ctl(plan, &ovf, &pl)) != hipSuccess) return e;
+      if ((e = read_ctl(&ovf, &pl)) != hipSuccess) return e;
       if (pl != kRsNoPlan && !ovf) return hipGetLastError();  // the carried plan stands for the next call too
       carry_set(CarriedPlan{0, -1, 0});
       if (pl != kRsNoPlan) skip_msd = true;  // a crowded bucket overflowed: straight to the LSD passes
       carried = true;
     }
-    const bool spec = !carried && hw && spec_env && split_env && msd_enabled(n, kSpecLo) &&
+    const bool spec = !carried && hw && msd_enabled(n, kSpecLo) &&
                       g_order_spec.load(std::memory_order_relaxed);
     if (((uintptr_t)col & 15) == 0 && ((uintptr_t)valid & 1) == 0)
       hipLaunchKernelGGL(k_rs_prep, dim3((unsigned)pb), dim3(256), 0, st, col, valid, n, desc, part);
@@ -1417,9 +1291,9 @@ hipError_t launch_ope_order(const int64_t* col, const uint8_t* valid, size_t n, 
       const uint64_t* plan = red + 2;
       const int rel[2] = {0, 8};
       run_passes(rel, 2, out_ids, ib, runs, true, valid != nullptr, false, 0, plan);
-      msd_tail(0, plan);
+      msd_tail(plan);
       uint64_t ovf = 0, pl = 0;
-      if ((e = read_ctl(plan, &ovf, &pl)) != hipSuccess) return e;
+      if ((e = read_ctl(&ovf, &pl)) != hipSuccess) return e;
       if (pl != kRsNoPlan && !ovf) return hipGetLastError();
       if (pl == kRsNoPlan) g_order_spec.store(0, std::memory_order_relaxed);
       else skip_msd = true;
@@ -1444,20 +1318,20 @@ hipError_t launch_ope_order(const int64_t* col, const uint8_t* valid, size_t n, 
     g_order_spec.store(sb >= kSpecLo && sb <= kSpecHi, std::memory_order_relaxed);
     // the next raw call may carry this plan (the MSD path below runs it with split keys and, with a
     // valid array, the key-bit validity: what the carried path runs)
-    const bool carriable = sb >= kSpecLo && sb <= kSpecHi && !skip_msd && msd_enabled(n, sb) && split_env &&
+    const bool carriable = sb >= kSpecLo && sb <= kSpecHi && !skip_msd && msd_enabled(n, sb) &&
                            (!valid || sb <= 56);
     carry_set(carriable ? CarriedPlan{kmin, sb - kMsdBits, desc} : CarriedPlan{0, -1, 0});
   }
   if (!skip_msd && msd_enabled(n, sb)) {
     runs.s1 = sb - kMsdBits;
     const int shifts[2] = {runs.s1, sb - 8};
-    const bool split = split_env && (!valid || kbit) && shifts[1] >= 32;
+    const bool split = (!valid || kbit) && shifts[1] >= 32;
     // grouped ids -> out_ids (one-key buckets are final there) + the bucket table; ib (the first pass's
     // ids) and kb are then free: the side copies of the multi-key buckets' ids and keys (k_msd_local)
     run_passes(shifts, 2, out_ids, ib, runs, split, kbit, vbit, kmin, nullptr);
-    msd_tail(kmin, nullptr);
+    msd_tail(nullptr);
     uint64_t ovf = 0, pl = 0;
-    if ((e = read_ctl(nullptr, &ovf, &pl)) != hipSuccess) return e;
+    if ((e = read_ctl(&ovf, &pl)) != hipSuccess) return e;
     if (!ovf) return hipGetLastError();
     // a bucket of > 8192 rows with > 16 distinct keys: redo the whole sort with the LSD passes
   }

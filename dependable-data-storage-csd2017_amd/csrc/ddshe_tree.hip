@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <map>
 #include <mutex>
@@ -259,7 +260,7 @@ __device__ __forceinline__ size_t node_row(int h, size_t i) { return (i << h) + 
 //   node's value (S limbs of W bits) to lvl_out[i * S] (next launch's leaves); 0: walk to the root.
 // At the root: finalize (Y != nullptr): out = canonical result, S limbs of W bits;
 //   else out = canonical partial, Sout limbs of Wout bits, consecutive.
-// fence_mode 0: every wave releases / acquires at agent scope around a hand-off; 1: wave 0 only.
+// fence_mode 2: sc1 write-through hand-off; 0: every wave releases / acquires at agent scope around a hand-off.
 template <int S, int W, int NT>
 __global__ void __launch_bounds__(NT) k_tree(const uint32_t* __restrict__ X, size_t xstride, size_t gstride,
                                                        int Sin, int Win, size_t nleaves,
@@ -380,12 +381,10 @@ __global__ void __launch_bounds__(NT) k_tree(const uint32_t* __restrict__ X, siz
       if (fence_mode == 0) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // every wave: its stores
       __syncthreads();
       if (tid == 0) {
-        if (fence_mode == 1) __threadfence();
         const uint32_t old = fence_mode == 2 ? __hip_atomic_fetch_add(flags + node_row(h + 1, i >> 1), 1u,
                                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                              : __hip_atomic_fetch_add(flags + node_row(h + 1, i >> 1), 1u,
                                                                       __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (fence_mode == 1) __threadfence();
         s_go = old != 0u;
       }
       __syncthreads();
@@ -503,10 +502,10 @@ Shape tree_shape(size_t mod_bits) {
 }
 
 // Launch plan of a tree over n leaves:
-//   * wide levels (more than DDSHE_TREE_WIDE blocks, default 256 = one per CU): one level per launch on
+//   * wide levels (more than kTreeWideBlocks blocks, 256 = one per CU): one level per launch on
 //     256-thread workgroups (k_tree<S, W, 256>): 8 products resident per CU instead of 1-2, each product
 //     slower than on 1024 threads but the level finishes in fewer rounds (512-thread workgroups for the
-//     levels of <= 1024 blocks measured the same, tools/tree_sweep.sh);
+//     levels of <= 1024 blocks measured the same, profiles/r03_tree_plan_sweep.txt);
 //   * the rest on 1024-thread workgroups, DDSHE_TREE_LEVELS levels per launch (0 = to the root).
 //     With in-kernel hand-offs (LEVELS != 1) the node words are handed over in the form MI355X_MICROARCH.md
 //     (§ inter-workgroup visibility, "Valid forms", first table row) lists as measured valid: every node
@@ -515,11 +514,8 @@ Shape tree_shape(size_t mod_bits) {
 //     returned 1 continues and its waves load the sibling with sc1 loads after a barrier; hipMalloc'd
 //     memory; ONE workgroup per CU, enforced by the launch's dynamic LDS (> half of the CU's 160 KiB).
 //     DDSHE_TREE_FENCE selects the hand-off style: 2 = that form, 0 = agent-scope release/acquire by
-//     every wave (L2 writeback + L1 invalidate per hop), 1 = one level per launch only.
-static int tree_env(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+//     every wave (L2 writeback + L1 invalidate per hop); any other value is read as 2.
+static int env_int(const char* e, int dflt) { return e ? atoi(e) : dflt; }
 
 // DDSHE_TREE_STAMPS=<file>: after every tree launch, synchronise and append one line per stamped block:
 // "S nleaves blocks block memtime_at_entry realtime_entry realtime_exit nmarks d1 d2 ..." (d = shader-clock
@@ -551,6 +547,7 @@ hipError_t launch_pairs_sos(int S, const uint32_t* A, const uint32_t* B, size_t 
 }
 
 constexpr int kTreeWideThreads = 256;
+constexpr size_t kTreeWideBlocks = 256;  // swept in round 3 (profiles/r03_tree_plan_sweep.txt)
 constexpr size_t kOneWgPerCuLds = 96 * 1024;  // dynamic LDS of a hand-off launch: one workgroup per CU
 
 // A hand-off launch asks for kOneWgPerCuLds of dynamic LDS on top of the kernel's static LDS (about
@@ -581,14 +578,15 @@ static bool handoff_fits(const void* fn) {
 hipError_t launch_tree(int S, const uint32_t* X, size_t xstride, int Sin, int Win, size_t nleaves, const uint32_t* ids,
                        const uint32_t* consts, const uint32_t* Y, uint32_t* nodes, uint32_t* flags, uint32_t* out,
                        int Sout, int Wout, hipStream_t st, size_t gstride, uint32_t* done, uint32_t seq) {
-  static const int levels_env = tree_env("DDSHE_TREE_LEVELS", 0), fence = tree_env("DDSHE_TREE_FENCE", 2);
-  static const size_t wide = (size_t)tree_env("DDSHE_TREE_WIDE", 256);
+  static const int levels_env = env_int(getenv("DDSHE_TREE_LEVELS"), 0);
+  static const int fence = [] {  // "0" alone selects style 0; anything else is read as 2
+    const char* e = getenv("DDSHE_TREE_FENCE");
+    return e && strcmp(e, "0") == 0 ? 0 : 2;
+  }();
+  constexpr size_t wide = kTreeWideBlocks;
   static uint64_t* d_st = nullptr;
   static const bool stamping = getenv("DDSHE_TREE_STAMPS") && hipMalloc(&d_st, 2 * kStamps * 8) == hipSuccess;
   if (nleaves == 0 || Sin > S + 64) return hipErrorInvalidValue;
-  // in-kernel hand-offs with wave-0-only fences rely on cache side effects the memory model does not
-  // promise: only the every-wave (0) and sc1 write-through (2) styles may hand off in-kernel
-  if (levels_env != 1 && fence == 1) return hipErrorInvalidValue;
   int levels = levels_env;
   if (levels != 1) DDSHE_TREE_SWITCH(S, if (!handoff_fits(reinterpret_cast<const void*>(&k_tree<S, W, kTreeThreads>))) levels = 1);
   // level buffers for multi-launch trees live after the nodes: two ping-pong halves of nleaves rows

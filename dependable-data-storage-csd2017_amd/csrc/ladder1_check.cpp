@@ -280,7 +280,7 @@ void check_exponent_rule() {
 
 void check_crt_consts() {
   const bn::Limbs n = bn::mul(kP, kQ), one{1};
-  const host::RsaCrtPlan pl = host::rsa_crt_plan(kP, kQ, pick, true, true);
+  const host::RsaCrtPlan pl = host::rsa_crt_plan(kP, kQ, pick, true);
   const host::ShapeSW sp = pick(bn::bit_length(kP)), sn = pick(bn::bit_length(n));
   const bn::Limbs Rp = bn::pow2((size_t)sp.S * sp.W), Rn = bn::pow2((size_t)sn.S * sn.W);
   const size_t lo = (size_t)pl.j * sn.W;
@@ -308,11 +308,11 @@ void check_crt_consts() {
 }
 
 void expect_plan(const char* name, const bn::Limbs& p, const bn::Limbs& q, int s1, int qp_p, int qp_q) {
-  const host::RsaCrtPlan pl = host::rsa_crt_plan(p, q, pick, true, true);
+  const host::RsaCrtPlan pl = host::rsa_crt_plan(p, q, pick, true);
   if (pl.s1[0] != s1 || pl.s1[1] != s1 || (s1 > 0 && (pl.qp[0] != qp_p || pl.qp[1] != qp_q)))
     die(std::string("plan of ") + name + ": got s1 = " + std::to_string(pl.s1[0]) + ", " + std::to_string(pl.s1[1]) +
         ", qp = " + std::to_string(pl.qp[0]) + ", " + std::to_string(pl.qp[1]));
-  const host::RsaCrtPlan off = host::rsa_crt_plan(p, q, pick, false, true);
+  const host::RsaCrtPlan off = host::rsa_crt_plan(p, q, pick, false);
   if (off.s1[0] > 0 || off.s1[1] > 0) die(std::string("plan of ") + name + ": ladder1 chosen while disabled");
   std::printf("ok plan %s: s1 = %d\n", name, s1);
 }

@@ -3,9 +3,7 @@ through rows_to_dec), bit-exact against Python's str(int), which is BigInteger.t
 value (the codec test relies on the same agreement in the other direction). Row format: DDSSet.scala:3,
 DDSJsonProtocol.scala:14-29; the encrypt that produces it: SJHomoLibProvider.scala:58.
 
-Every column shape runs (S = 40 ... 640 limbs) except S = 74, which a process only uses with DDSHE_RSA76=0
-set before the library loads: the print kernel takes the limb count as a run-time argument, and
-csrc/dec_check.cpp replays its row routine for that shape on the CPU."""
+Every column shape runs (S = 40 ... 640 limbs); no column has S = 74."""
 import ctypes
 import random
 import sys

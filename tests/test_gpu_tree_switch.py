@@ -2,8 +2,7 @@
 tree's 4096 leaves' worth of lane groups: 4160 / 4480 groups, the full group count with two rows per
 group, the strong-split share size). SumAll (DDSRestServer.scala:412-430) must stay bit-exact against the
 oracle's fold, or Dec(fold) = Σm on synthetic Paillier rows under the committed key, and the device-partial
-path must equal the fold. tools/gpurun/inblock_ab.sh also runs this file with DDSHE_FOLD_INBLOCK=1 (level
-1 folding each block's partials through LDS, k_fold InBlock: an A/B option, slower, off by default)."""
+path must equal the fold."""
 import random
 
 import numpy as np
@@ -15,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("k", [8_320, 9_001, 65_539])
-def test_inblock_fold_vs_oracle(eng, keys, k):
+def test_tree_switch_fold_vs_oracle(eng, keys, k):
     key = keys["paillier2048_committed"]
     N = key["nsquare"]
     rng = random.Random(k)
@@ -30,7 +29,7 @@ def test_inblock_fold_vs_oracle(eng, keys, k):
 
 
 @pytest.mark.parametrize("rows", [300_007, 1_250_000])
-def test_inblock_fold_decrypts_and_partial_matches(eng, keys, rows):
+def test_tree_switch_fold_decrypts_and_partial_matches(eng, keys, rows):
     import torch
     key = keys["paillier2048_committed"]
     N = key["nsquare"]

@@ -1,5 +1,5 @@
-"""Summarise OrderLS A/B runs (tools/gpurun/order_ab.sh): the bench line of each variant and the
-per-kernel device time of the last OrderLS call in its rocprofv3 kernel trace."""
+"""Summarise OrderLS A/B runs (a bench log and a rocprofv3 kernel trace per variant): the bench line of
+each variant and the per-kernel device time of the last OrderLS call in its rocprofv3 kernel trace."""
 import csv
 import json
 import sys

@@ -1,7 +1,7 @@
 """A/B probe of the 8-GPU strong-split share on one GPU: one share of the
 10M-row headline (1.25M rows, committed 2048-bit key) folded to a device partial
 (dds_col_fold_partial_device); prints the share's wall time, its level-1 launch (HIP events) and the
-tail. Run under DDSHE_PARTIAL_GROUPS=<cap> to cap level 1's lane groups (0: the engine's plan)."""
+tail."""
 import json
 import os
 import sys
@@ -46,6 +46,6 @@ eng.set_timing(False)
 first = buf.cpu().numpy().tobytes()
 ok = eng.combine_partials_device(k["nsquare"], buf.data_ptr(), [rows]) == col.fold(0, rows)
 lvl = lvl_ms / lvl_n if lvl_n else None
-print(json.dumps({"groups_cap": int(os.environ.get("DDSHE_PARTIAL_GROUPS", "0")), "rows": rows,
+print(json.dumps({"rows": rows,
                   "share_ms": ts[len(ts) // 2], "share_min_ms": ts[0], "level1_ms": lvl,
                   "tail_ms": ts[len(ts) // 2] - lvl if lvl else None, "partial_matches_fold": ok}))
