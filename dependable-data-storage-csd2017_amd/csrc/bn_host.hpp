@@ -418,6 +418,47 @@ inline uint32_t mont_n0(uint32_t n_low, int W) {
   return (0u - inv) & ((1u << W) - 1);
 }
 
+// a⁻¹ mod m by the extended Euclid (bn::mod returns the quotients); false when gcd(a, m) != 1 or a ≡ 0.
+// The Bezout coefficients alternate in sign, so their magnitudes only ever add: r_i ≡ ±t_i·a (mod m).
+inline bool inv_mod(const Limbs& a, const Limbs& m, Limbs* out) {
+  if (m.empty()) return false;
+  Limbs r0 = m, r1 = mod(a, m), t0, t1{1};
+  if (r1.empty()) return false;
+  bool pos1 = true;  // the sign of t1; t0 has the other one
+  while (!r1.empty()) {
+    Limbs q;
+    Limbs r2 = mod(r0, r1, &q);
+    Limbs t2 = add(t0, mul(q, t1));
+    r0.swap(r1);
+    r1.swap(r2);
+    t0.swap(t1);
+    t1.swap(t2);
+    pos1 = !pos1;
+  }
+  if (cmp(r0, Limbs{1}) != 0) return false;
+  t0 = mod(t0, m);
+  *out = (!pos1 || t0.empty()) ? t0 : sub(m, t0);
+  return true;
+}
+
+// The host end of a batch inversion mod n (ddshe_foldunit.hpp): out[i] = Rmod·t_i⁻¹ mod n for the totals t
+// (any residues), with one inv_mod of their product and three products per total. False when a total is no
+// unit mod n (the product is a unit iff every factor is); out is then untouched.
+inline bool inv_finish(const std::vector<Limbs>& t, const Limbs& n, const Limbs& Rmod, std::vector<Limbs>* out) {
+  std::vector<Limbs> pre(t.size() + 1);
+  pre[0] = mod(Limbs{1}, n);
+  for (size_t i = 0; i < t.size(); ++i) pre[i + 1] = mulmod(pre[i], t[i], n);
+  Limbs g;
+  if (!inv_mod(pre[t.size()], n, &g)) return false;
+  g = mulmod(g, Rmod, n);  // Rmod / (t_0 ... t_i), walking i down
+  out->assign(t.size(), Limbs());
+  for (size_t i = t.size(); i-- > 0;) {
+    (*out)[i] = mulmod(g, pre[i], n);
+    g = mulmod(g, t[i], n);
+  }
+  return true;
+}
+
 // floor(sqrt(a)) (Newton from above: x <- (x + a / x) / 2 until it stops decreasing)
 inline Limbs isqrt(const Limbs& a) {
   if (a.empty()) return a;
@@ -434,11 +475,11 @@ inline Limbs isqrt(const Limbs& a) {
 
 // Constants of the base-n digit form of arithmetic mod N = n² (ddshe_foldsq.hpp), digits of s limbs of
 // W bits, R = 2^(W·s): k = -n⁻¹ mod 2^W; ñ = k·n ≡ -1 mod 2^W (the QP modulus of n); C = -k·(R - 1)
-// mod n; R mod n. sq_consts returns false unless N is an odd perfect square with
+// mod n; R mod n; R² mod n. sq_consts returns false unless N is an odd perfect square with
 // bits(n) <= W·s - W - 2 (then R > 4ñ and the digits, kept < 2ñ, fit s limbs).
 struct SqDigits {
   uint32_t k = 0;
-  Limbs n, nq, C, Rmod;
+  Limbs n, nq, C, Rmod, R2;
 };
 inline bool sq_consts(const Limbs& N, int s, int W, SqDigits* out) {
   if (N.empty() || (N[0] & 1u) == 0) return false;
@@ -452,6 +493,7 @@ inline bool sq_consts(const Limbs& N, int s, int W, SqDigits* out) {
   d.nq = mul(d.n, Limbs{d.k});
   const Limbs R = pow2((size_t)W * s);
   d.Rmod = mod(R, d.n);
+  d.R2 = mod(mul(d.Rmod, d.Rmod), d.n);
   const Limbs t = mod(mul(Limbs{d.k}, sub(R, Limbs{1})), d.n);  // k·(R - 1) mod n
   d.C = t.empty() ? t : sub(d.n, t);
   *out = d;

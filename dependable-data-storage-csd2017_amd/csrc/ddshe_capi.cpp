@@ -151,7 +151,7 @@ int get_mod(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, std::shared_p
     bn::SqDigits sd;
     if (bn::sq_consts(N, kFoldSqLimbs, mc->W, &sd)) {
       std::vector<uint32_t> h;
-      for (const bn::Limbs* v : {&sd.nq, &sd.n, &sd.C, &sd.Rmod}) {  // kSqNq, kSqN, kSqC, kSqRmod
+      for (const bn::Limbs* v : {&sd.nq, &sd.n, &sd.C, &sd.Rmod, &sd.R2}) {  // kSqNq, kSqN, kSqC, kSqRmod, kSqR2
         const std::vector<uint32_t> r = bn::to_rw(*v, kFoldSqLimbs, mc->W);
         h.insert(h.end(), r.begin(), r.end());
       }
@@ -247,6 +247,91 @@ constexpr size_t kTreeSwitchLeaves = 4096;
 // group, straight from the main-shape rows
 constexpr size_t kNarrowFoldRows = 65536;
 
+namespace {
+
+hipError_t ensure_raw(DevBufRaw& b, size_t bytes) {
+  if (bytes <= b.cap) return hipSuccess;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.cap = 0;
+  const hipError_t e = hipMalloc(&b.p, bytes);
+  if (e == hipSuccess) b.cap = bytes;
+  else b.p = nullptr;
+  return e;
+}
+
+// Before published rows of the mirror are rewritten: wait until every fold that was handed the mirror has
+// launched its kernels (it then drops its copy of the token; new copies need sqmu, which the caller
+// holds), and then for the device.
+void mirror_quiesce(dds_col* col) {
+  while (col->mirror_token.use_count() > 1) std::this_thread::yield();
+  std::atomic_thread_fence(std::memory_order_acquire);
+  (void)hipDeviceSynchronize();
+}
+
+// Rows [r0, r1) of the mirror, plane 1: c -> b = c·w⁻¹ mod n, by one batch inversion per chunk of
+// kInvChunkRows rows: GPU levels of kInvFan rows per group until at most kInvFan totals remain, which
+// the host inverts (bn::inv_finish). 0: done (stream synchronised); 1: some w of the range is no unit mod n
+// (plane 1 of the range is then part c, part b); -1: a HIP call failed.
+int unit_upgrade(dds_col* col, hipStream_t st, size_t r0, size_t r1) {
+  ModConsts& mc = *col->mc;
+  constexpr int S = kFoldSqLimbs;
+  const uint32_t k = mc.sq->k;
+  for (size_t a = r0; a < r1; a += kInvChunkRows) {
+    const size_t n0 = std::min(kInvChunkRows, r1 - a);
+    std::vector<size_t> cnt{n0};  // cnt[i]: rows of level i = groups of level i - 1
+    do cnt.push_back((cnt.back() + kInvFan - 1) / kInvFan);
+    while (cnt.back() > kInvFan);
+    const size_t nl = cnt.size() - 1;
+    std::vector<size_t> off(nl + 1, 0);  // level i >= 1: planes T, Pfx, V of S limb rows at round_up(cnt[i], 64)
+    size_t words = 0;
+    for (size_t i = 1; i <= nl; ++i) {
+      off[i] = words;
+      words += (size_t)3 * S * round_up(cnt[i], 64);
+    }
+    if (ensure_raw(col->inv_pfx, (size_t)S * round_up(n0, 64) * 4) != hipSuccess ||
+        ensure_raw(col->inv_lv, words * 4) != hipSuccess) {
+      (void)hipGetLastError();
+      return -1;
+    }
+    uint32_t* lv = (uint32_t*)col->inv_lv.p;
+    auto strd = [&](size_t i) { return i == 0 ? col->stride : round_up(cnt[i], 64); };
+    auto Tp = [&](size_t i) { return i == 0 ? col->digits + a : lv + off[i]; };
+    auto Pf = [&](size_t i) { return i == 0 ? (uint32_t*)col->inv_pfx.p : lv + off[i] + (size_t)S * strd(i); };
+    auto Vp = [&](size_t i) { return lv + off[i] + (size_t)2 * S * strd(i); };
+    auto pfs = [&](size_t i) { return i == 0 ? round_up(n0, 64) : strd(i); };
+    for (size_t i = 0; i < nl; ++i)
+      if (launch_inv_up(Tp(i), strd(i), cnt[i], mc.dsq, k, Pf(i), pfs(i), Tp(i + 1), strd(i + 1), cnt[i + 1], st) !=
+          hipSuccess)
+        return -1;
+    const size_t ts = strd(nl), m = cnt[nl];
+    std::vector<uint32_t> h((size_t)S * ts), limbs(S);
+    if (hipMemcpyAsync(h.data(), Tp(nl), h.size() * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+      return -1;
+    std::vector<bn::Limbs> tot(m), rinv;
+    for (size_t g = 0; g < m; ++g) {
+      for (int l = 0; l < S; ++l) limbs[l] = h[(size_t)l * ts + g];
+      tot[g] = bn::from_rw(limbs.data(), S, mc.W);
+    }
+    if (!bn::inv_finish(tot, mc.sq->n, mc.sq->Rmod, &rinv)) return 1;
+    for (size_t g = 0; g < m; ++g) {
+      const std::vector<uint32_t> r = bn::to_rw(rinv[g], S, mc.W);
+      for (int l = 0; l < S; ++l) h[(size_t)l * ts + g] = r[l];
+    }
+    if (hipMemcpyAsync(Vp(nl), h.data(), h.size() * 4, hipMemcpyHostToDevice, st) != hipSuccess) return -1;
+    for (size_t i = nl; i-- > 0;)
+      if (launch_inv_down(Tp(i), strd(i), cnt[i], mc.dsq, k, Pf(i), pfs(i), Vp(i + 1), strd(i + 1),
+                          i == 0 ? col->digits + (size_t)S * col->stride + a : nullptr, col->stride,
+                          i == 0 ? nullptr : Vp(i), strd(i), cnt[i + 1], st) != hipSuccess)
+        return -1;
+    if (hipStreamSynchronize(st) != hipSuccess) return -1;  // h goes, and the next chunk reuses the scratch
+  }
+  return 0;
+}
+
+}  // namespace
+
 FoldDigits col_fold_digits(dds_col* col, hipStream_t st, size_t first, size_t count, const uint32_t* d_ids) {
   ModConsts& mc = *col->mc;
   if (!mc.sq || d_ids || !fold_sq_enabled() || count < fold_sq_min_rows(col->ctx->cus)) return FoldDigits();
@@ -259,16 +344,41 @@ FoldDigits col_fold_digits(dds_col* col, hipStream_t st, size_t first, size_t co
     return FoldDigits();
   }
   const size_t end = first + count;
-  if (col->digits_rows < end) {
-    // the watermark is published only once the rows are converted: a concurrent fold reads the mirror
-    // on another stream
+  // the watermarks are published only once the rows are converted: a concurrent fold reads the mirror
+  // on another stream
+  auto convert_to = [&](size_t to) {
     const size_t r0 = col->digits_rows;
-    if (launch_to_digits(col->d + r0, col->stride, end - r0, mc.dsq, mc.sq->k, col->digits + r0, st) != hipSuccess ||
+    if (launch_to_digits(col->d + r0, col->stride, to - r0, mc.dsq, mc.sq->k, col->digits + r0, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-      return FoldDigits();
-    col->digits_rows = end;
+      return false;
+    col->digits_rows = to;
+    return true;
+  };
+  const bool hit = col->digits_rows >= end;
+  if (!hit && !convert_to(end)) return FoldDigits();
+  const int h = fold_unit_after();
+  if (hit && h > 0 && !col->unit_mode && !col->unit_failed && ++col->mirror_hits >= (unsigned)h) {
+    mirror_quiesce(col);  // plain folds in flight read the c this fold is about to replace
+    col->unit_mode = true;
   }
-  return FoldDigits{col->digits + first, col->stride};
+  if (col->unit_mode) {
+    const int rc = col->unit_rows < end ? unit_upgrade(col, st, col->unit_rows, end) : 0;
+    if (rc == 0) {
+      col->unit_rows = std::max(col->unit_rows, end);
+      return FoldDigits{col->digits + first, col->stride, true, col->mirror_token};
+    }
+    // plane 1 past unit_rows is part c, part b. A failed HIP call leaves the fold on the opaque path and the
+    // rows to be converted again; a non-unit takes the column out of unit mode for good (until it is
+    // emptied) and rebuilds the plain digits from row 0, once no unit fold reads the b below unit_rows
+    col->digits_rows = std::min(col->digits_rows, col->unit_rows);
+    if (rc < 0) return FoldDigits();
+    col->unit_mode = false;
+    col->unit_failed = true;
+    mirror_quiesce(col);
+    col->unit_rows = col->digits_rows = 0;
+    if (!convert_to(end)) return FoldDigits();
+  }
+  return FoldDigits{col->digits + first, col->stride, false, col->mirror_token};
 }
 
 // Level 1 (throughput shape, G groups: group g holds prod_g * R^(1 - c_g)) over `count` rows of X (or
@@ -282,10 +392,15 @@ int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const ui
     const size_t gmax = fold_sq_max_groups(ctx->cus);
     const size_t G = std::min(gmax, std::max<size_t>(1, count / 2)), ps = round_up(G, 64);
     HIP_TRY(w->p0.ensure((size_t)S2 * ps * 4));
-    HIP_TRY(w->sqp.ensure((size_t)2 * kFoldSqLimbs * ps * 4));
+    HIP_TRY(w->sqp.ensure((size_t)3 * kFoldSqLimbs * ps * 4));  // x0, x1 and, in unit form, S
     record_time(ctx, w, st, true, 0);
-    HIP_TRY(launch_fold_sq(dg.D, dg.stride, count, mc.dsq, mc.sq->k, w->sqp.as<uint32_t>(), ps, G, st));
+    if (dg.unit)
+      HIP_TRY(launch_fold_unit(dg.D, dg.stride, count, mc.dsq, mc.sq->k, w->sqp.as<uint32_t>(), ps, G, st));
+    else
+      HIP_TRY(launch_fold_sq(dg.D, dg.stride, count, mc.dsq, mc.sq->k, w->sqp.as<uint32_t>(), ps, G, st));
     record_time(ctx, w, st, false, 0);
+    // unit form: x1 += x0·S, after which a group is what the plain form left (same power of R)
+    if (dg.unit) HIP_TRY(launch_unit_join(w->sqp.as<uint32_t>(), ps, G, mc.dsq, mc.sq->k, st));
     if (ctx->timing.load()) {
       w->timed_fold = true;
       std::lock_guard<std::mutex> lk(ctx->tmu);
@@ -1774,6 +1889,13 @@ size_t dds_col_digit_rows(dds_col* col) {
   std::shared_lock<std::shared_mutex> lk(col->mu);
   std::lock_guard<std::mutex> ls(col->sqmu);
   return col->digits ? col->digits_rows : 0;
+}
+
+size_t dds_col_unit_rows(dds_col* col) {
+  if (!col) return 0;
+  std::shared_lock<std::shared_mutex> lk(col->mu);
+  std::lock_guard<std::mutex> ls(col->sqmu);
+  return col->digits ? col->unit_rows : 0;
 }
 
 size_t dds_col_partial_words(const dds_col* col) { return col ? partial_words_for(*col->mc) : 0; }

@@ -282,6 +282,11 @@ struct dds_ctx {
   ~dds_ctx();
 };
 
+struct DevBufRaw {  // a device allocation grown on demand, freed by its owner
+  void* p = nullptr;
+  size_t cap = 0;
+};
+
 struct dds_col {
   dds_ctx* ctx = nullptr;
   std::shared_ptr<ddshe::host::ModConsts> mc;
@@ -317,9 +322,25 @@ struct dds_col {
   size_t digits_rows = 0;
   bool digits_failed = false;
   std::mutex sqmu;
+  // Unit form of the mirror (ddshe_foldunit.hpp): rows [0, unit_rows) hold b ≡ c·w⁻¹ (mod n) in plane 1,
+  // rows [unit_rows, digits_rows) still hold c; unit_rows <= digits_rows, lowered together with it. A
+  // column enters unit mode at its fold_unit_after()-th mirror hit (a fold that found every row of its
+  // range converted); from then on a mirror fold first upgrades the rows of its range past unit_rows and
+  // runs k_fold_unit. A batch with a row whose w is no unit mod n publishes nothing: unit_failed keeps the
+  // column on k_fold_sq until it is emptied, and the plain digits are rebuilt from row 0. All under sqmu.
+  size_t unit_rows = 0;
+  bool unit_mode = false, unit_failed = false;
+  unsigned mirror_hits = 0;
+  DevBufRaw inv_pfx, inv_lv;  // upgrade scratch: prefix products of a chunk, the upper levels' planes
+  // Every fold that reads the mirror holds a copy for as long as it may still launch kernels over it. A
+  // rewrite of published rows (entering unit mode, the rebuild after a failed batch) waits until it is the
+  // only holder and then for the device: copies are only handed out under sqmu, which the rewriter holds.
+  std::shared_ptr<int> mirror_token = std::make_shared<int>(0);
   ~dds_col() {
     if (d) (void)hipFree(d);
     if (digits) (void)hipFree(digits);
+    if (inv_pfx.p) (void)hipFree(inv_pfx.p);
+    if (inv_lv.p) (void)hipFree(inv_lv.p);
     if (dlive) (void)hipFree(dlive);
   }
 };
@@ -330,7 +351,8 @@ namespace host {
 
 // The column lock held exclusively by a mutation. When it ends, the digit mirror's watermark drops to
 // the first row the holder may have changed: row 0 unless the holder says otherwise (touches_from), so a
-// writer that says nothing costs a re-conversion, never a stale digit. This is the only place the
+// writer that says nothing costs a re-conversion, never a stale digit. The unit-form watermark drops with
+// it. Apart from the rebuild after a failed inversion (col_fold_digits) this is the only place the
 // watermark is lowered.
 struct ColWriteLock {
   static constexpr size_t kNoRow = ~(size_t)0;  // no stored row changed (liveness only)
@@ -344,7 +366,13 @@ struct ColWriteLock {
   // rows below `row` keep their value (an append: the row count when the lock was taken)
   void touches_from(size_t row) { first = row; }
   ~ColWriteLock() {
-    if (lk.owns_lock()) col->digits_rows = std::min(col->digits_rows, first);
+    if (!lk.owns_lock()) return;
+    col->digits_rows = std::min(col->digits_rows, first);
+    col->unit_rows = std::min(col->unit_rows, first);
+    if (col->count == 0) {  // emptied: a later batch may be all units
+      col->unit_failed = false;
+      col->mirror_hits = 0;
+    }
   }
 };
 
@@ -611,6 +639,8 @@ struct Leaves {
 struct FoldDigits {
   const uint32_t* D = nullptr;
   size_t stride = 0;
+  bool unit = false;          // plane 1 holds b (unit form): level 1 is k_fold_unit
+  std::shared_ptr<int> hold;  // dds_col::mirror_token, kept until the fold has launched its kernels
 };
 // Brings the mirror of `col` up to row first + count and returns it at row `first`; an empty FoldDigits
 // when the column, the fold size or DDSHE_FOLD_SQ rules the digit form out (never an error: the fold

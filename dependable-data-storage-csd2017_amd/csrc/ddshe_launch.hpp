@@ -48,11 +48,11 @@ hipError_t launch_fold(int S, const uint32_t* X, size_t xstride, size_t count, c
                        int lane1 = 0);  // != 0: one bignum per lane (k_fold1) at lane1 = fold1_limbs(S, bits) limbs
 // Digit-form fold of a perfect-square modulus n² in the (148, 4, 28) shape (ddshe_foldsq.hpp): values as
 // two base-n digits of kFoldSqLimbs limbs each. sq: kSqCount vectors of kFoldSqLimbs limbs (ñ = k·n | n |
-// C | R mod n), k = -n⁻¹ mod 2^28. The mirror D and the digit partials Q are limb-major, 2·kFoldSqLimbs
+// C | R mod n | R² mod n), k = -n⁻¹ mod 2^28. The mirror D and the digit partials Q are limb-major, 2·kFoldSqLimbs
 // limb rows (digit 0, then digit 1). DDSHE_FOLD_SQ=0 disables the path, DDSHE_FOLD_SQ_MIN=<rows>
 // overrides the row count from which a fold takes it.
 constexpr int kFoldSqLimbs = 76, kFoldSqWide = 148;
-enum { kSqNq = 0, kSqN = 1, kSqC = 2, kSqRmod = 3, kSqCount = 4 };
+enum { kSqNq = 0, kSqN = 1, kSqC = 2, kSqRmod = 3, kSqR2 = 4, kSqCount = 5 };  // kSqR2: R² mod n
 bool fold_sq_enabled();
 size_t fold_sq_min_rows(int cus);
 size_t fold_sq_max_groups(int cus);
@@ -63,6 +63,31 @@ hipError_t launch_fold_sq(const uint32_t* D, size_t stride, size_t count, const 
 // digit partials -> X = w + (c mod n)·n < 2N in s_out (= 160) limbs, limb-major at pstride
 hipError_t launch_sq_join(const uint32_t* Q, size_t qstride, size_t ngroups, const uint32_t* sq, uint32_t k,
                           uint32_t* P, size_t pstride, int s_out, hipStream_t st);
+// Unit form of the mirror (ddshe_foldunit.hpp): plane 1 of a row holds b ≡ c·w⁻¹ (mod n) instead of c, so
+// the fold multiplies by the one digit w and sums the b. DDSHE_FOLD_UNIT_AFTER=<h>: a column enters it at
+// its h-th mirror hit (default 2, 0: never).
+int fold_unit_after();
+// rows per group of one inversion level, and the row count at or below which the host finishes
+constexpr size_t kInvFan = 32;
+// rows whose prefix products one upgrade pass holds in scratch (kFoldSqLimbs limbs each)
+constexpr size_t kInvChunkRows = (size_t)1 << 20;
+// rows per group k_fold_unit admits: the sum of the b stays below R
+constexpr size_t kFoldUnitMaxRowsPerGroup = (size_t)1 << 26;
+// Up pass of a batch inversion mod n over rows [0, count) of the digit plane Wp: Pfx[., row] = the product
+// of the group's rows before `row` (times R, Montgomery), T[., g] = the group's total. Group g: rows g, g + G, ...
+hipError_t launch_inv_up(const uint32_t* Wp, size_t wstride, size_t count, const uint32_t* sq, uint32_t k,
+                         uint32_t* Pfx, size_t pstride, uint32_t* T, size_t tstride, size_t ngroups, hipStream_t st);
+// Down pass: V[., g] = R/T_g. With C (plane 1 of the same rows) it overwrites c with b = c/w, else it
+// writes R/w to Inv.
+hipError_t launch_inv_down(const uint32_t* Wp, size_t wstride, size_t count, const uint32_t* sq, uint32_t k,
+                           const uint32_t* Pfx, size_t pstride, const uint32_t* V, size_t vstride, uint32_t* C,
+                           size_t cstride, uint32_t* Inv, size_t istride, size_t ngroups, hipStream_t st);
+// Level 1 over a unit-form mirror: Q gets 3·kFoldSqLimbs limb rows per group (x0, x1, S = Σ b)
+hipError_t launch_fold_unit(const uint32_t* D, size_t stride, size_t count, const uint32_t* sq, uint32_t k, uint32_t* Q,
+                            size_t qstride, size_t ngroups, hipStream_t st);
+// x1 <- x1 + x0·S (mod n, literal) in place: Q is then what launch_sq_join takes
+hipError_t launch_unit_join(uint32_t* Q, size_t qstride, size_t ngroups, const uint32_t* sq, uint32_t k,
+                            hipStream_t st);
 // k_fold1 (one bignum per lane) exists for S (40, 76) and is worth its longer per-product latency for
 // folds of at least fold1_min_rows(S) rows (DDSHE_FOLD1=0 disables it, DDSHE_FOLD1_MIN=<rows> overrides)
 bool fold1_shape(int S);

@@ -58,6 +58,7 @@ EXPORTS = [
     "dds_mcol_fold", "dds_mcol_fold_rows", "dds_mcol_fold_dec",
     "dds_pair_modmul_dec", "dds_pair_stats", "dds_pair_timing", "dds_pair_set_policy", "dds_pair_cpu",
     "dds_col_write_rows", "dds_col_write_rows_dec", "dds_col_set_live", "dds_col_live_count", "dds_col_digit_rows",
+    "dds_col_unit_rows",
     "dds_mcol_write_rows", "dds_mcol_write_rows_dec", "dds_mcol_set_live", "dds_mcol_live_count",
     "dds_opecol_write_rows", "dds_opecol_write_rows_dec", "dds_opecol_set_live", "dds_opecol_live_count",
     "dds_opecol_search_mask", "dds_ctx_cache_stats",
@@ -101,6 +102,7 @@ _sig("dds_col_append", C.c_int, C.c_void_p, C.c_char_p, _sz, _sz)
 _sig("dds_col_append_dec", C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_uint64), _sz)
 _sig("dds_col_count", _sz, C.c_void_p)
 _sig("dds_col_digit_rows", _sz, C.c_void_p)
+_sig("dds_col_unit_rows", _sz, C.c_void_p)
 _sig("dds_col_truncate", C.c_int, C.c_void_p, _sz)
 _sig("dds_col_read", C.c_int, C.c_void_p, _sz, _sz, _u8p)
 _sig("dds_col_dec_width", _sz, C.c_void_p)
@@ -650,6 +652,11 @@ class Column(_Mutable):
     def digit_rows(self) -> int:
         """dds_col_digit_rows: rows of the base-n digit mirror that are current (0: no mirror in use)."""
         return _lib.dds_col_digit_rows(self._h)
+
+    @property
+    def unit_rows(self) -> int:
+        """dds_col_unit_rows: rows of the mirror that are in unit form (0: not upgraded, or a non-unit row)."""
+        return _lib.dds_col_unit_rows(self._h)
 
     def append(self, ops):
         ops = [int(x) for x in ops]

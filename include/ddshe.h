@@ -205,6 +205,12 @@ size_t dds_col_live_count(dds_col* col);
  * mutations lower n, the next fold converts what it needs. 0: no mirror (other moduli, short folds only,
  * DDSHE_FOLD_SQ=0, or the allocation failed and the column folds as before). See INTEGRATION.md. */
 size_t dds_col_digit_rows(dds_col* col);
+/* Rows [0, n) of the mirror that are in unit form (n <= dds_col_digit_rows): their second digit c is replaced
+ * by b = c/w mod n, which lets a fold multiply by one digit and sum the b. A column's mirror is upgraded at
+ * its DDSHE_FOLD_UNIT_AFTER-th fold that found every row converted (default 2, 0: never) and kept current like
+ * the digits. 0: not upgraded, or a row's first digit is no unit mod n (the column then folds in plain
+ * digits until it is emptied). */
+size_t dds_col_unit_rows(dds_col* col);
 /* download rows [first, first+count) as canonical residues (x mod N), big-endian, mod_bytes each */
 int dds_col_read(dds_col* col, size_t first, size_t count, uint8_t* out);
 /* ---- decimal egress: rows out as the text the store holds ----
