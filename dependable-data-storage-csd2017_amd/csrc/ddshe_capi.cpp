@@ -389,12 +389,17 @@ int fold_level1(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const ui
                 size_t count, const uint32_t* d_ids, Leaves* lv, const FoldDigits& dg) {
   const int S = mc.S, S2 = mc.S2;
   if (dg.D && !d_ids && mc.sq && count >= 2) {
-    const size_t gmax = fold_sq_max_groups(ctx->cus);
+    // unit form, many rows per group: one chain per lane (k_fold_unit1), with its own group limit
+    const bool unit1 = dg.unit && count >= fold_unit1_min_rows(ctx->cus) && count <= kFoldUnit1MaxRows &&
+                       dg.stride <= kFoldUnit1MaxStride;
+    const size_t gmax = unit1 ? fold_unit1_max_groups(ctx->cus) : fold_sq_max_groups(ctx->cus);
     const size_t G = std::min(gmax, std::max<size_t>(1, count / 2)), ps = round_up(G, 64);
     HIP_TRY(w->p0.ensure((size_t)S2 * ps * 4));
     HIP_TRY(w->sqp.ensure((size_t)3 * kFoldSqLimbs * ps * 4));  // x0, x1 and, in unit form, S
     record_time(ctx, w, st, true, 0);
-    if (dg.unit)
+    if (unit1)
+      HIP_TRY(launch_fold_unit1(dg.D, dg.stride, count, mc.dsq, mc.sq->k, w->sqp.as<uint32_t>(), ps, G, st));
+    else if (dg.unit)
       HIP_TRY(launch_fold_unit(dg.D, dg.stride, count, mc.dsq, mc.sq->k, w->sqp.as<uint32_t>(), ps, G, st));
     else
       HIP_TRY(launch_fold_sq(dg.D, dg.stride, count, mc.dsq, mc.sq->k, w->sqp.as<uint32_t>(), ps, G, st));

@@ -1,8 +1,10 @@
-// Launchers of the unit-form fold and of the batch inversion mod n behind it (ddshe_foldunit.hpp), in the
-// half shape (76, 4, 28) of the digit form.
+// Launchers of the unit-form fold (ddshe_foldunit.hpp, and ddshe_foldunit1.hpp at one chain per lane) and of
+// the batch inversion mod n behind it, in the half shape (76, 4, 28) of the digit form.
+#include <algorithm>
 #include <cstdlib>
 
 #include "ddshe_foldunit.hpp"
+#include "ddshe_foldunit1.hpp"
 #include "ddshe_launch.hpp"
 #include "ddshe_shapes.hpp"
 
@@ -47,6 +49,44 @@ hipError_t launch_fold_unit(const uint32_t* D, size_t stride, size_t count, cons
   if ((count + ngroups - 1) / ngroups > kFoldUnitMaxRowsPerGroup) return hipErrorInvalidValue;
   hipLaunchKernelGGL((k_fold_unit<kS, kTPI, kW>), dim3(grid_for(ngroups * kTPI)), dim3(256), 0, st, D, stride, count,
                      sq, k, Q, qstride, ngroups);
+  return hipGetLastError();
+}
+
+// A product takes twice as long per lane at one chain per lane, so folds with few rows per pair lose what
+// the denser issue gains. DDSHE_FOLD_UNIT1=0 keeps every fold on k_fold_unit, DDSHE_FOLD_UNIT1_MIN=<rows>
+// overrides the row count from which a fold takes k_fold_unit1.
+size_t fold_unit1_min_rows(int cus) {
+  static const bool on = [] {
+    const char* e = getenv("DDSHE_FOLD_UNIT1");
+    return !(e && e[0] == '0');
+  }();
+  static const long long env = [] {
+    const char* e = getenv("DDSHE_FOLD_UNIT1_MIN");
+    return e ? atoll(e) : -1ll;
+  }();
+  if (!on) return (size_t)-1;
+  if (env >= 0) return (size_t)std::max(env, 2ll);
+  return (size_t)kFoldUnit1RowsPerPair * fold_unit1_max_groups(cus);
+}
+
+size_t fold_unit1_max_groups(int cus) {
+  static const int bpc = [] {
+    int b = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void*)k_fold_unit1<kS, kW>, 256, 0) != hipSuccess ||
+        b < 1)
+      b = 1;
+    return b;
+  }();
+  return (size_t)cus * bpc * (256 / 2);
+}
+
+hipError_t launch_fold_unit1(const uint32_t* D, size_t stride, size_t count, const uint32_t* sq, uint32_t k,
+                             uint32_t* Q, size_t qstride, size_t ngroups, hipStream_t st) {
+  if (ngroups == 0 || ngroups > count || qstride < ngroups) return hipErrorInvalidValue;
+  if ((count + ngroups - 1) / ngroups > kFoldUnitMaxRowsPerGroup) return hipErrorInvalidValue;
+  if (count > kFoldUnit1MaxRows || stride > kFoldUnit1MaxStride) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((k_fold_unit1<kS, kW>), dim3(grid_for(ngroups * 2)), dim3(256), 0, st, D, stride, count, sq, k,
+                     Q, qstride, ngroups);
   return hipGetLastError();
 }
 

@@ -85,6 +85,18 @@ hipError_t launch_inv_down(const uint32_t* Wp, size_t wstride, size_t count, con
 // Level 1 over a unit-form mirror: Q gets 3·kFoldSqLimbs limb rows per group (x0, x1, S = Σ b)
 hipError_t launch_fold_unit(const uint32_t* D, size_t stride, size_t count, const uint32_t* sq, uint32_t k, uint32_t* Q,
                             size_t qstride, size_t ngroups, hipStream_t st);
+// The same fold at one chain per lane (ddshe_foldunit1.hpp: a pair of lanes per group, S in LDS), same Q.
+// Taken from fold_unit1_min_rows rows upwards (DDSHE_FOLD_UNIT1=0 disables it, DDSHE_FOLD_UNIT1_MIN=<rows>
+// overrides), with up to fold_unit1_max_groups pairs.
+constexpr size_t kFoldUnit1RowsPerPair = 16;
+// its row loop runs on 32-bit byte offsets (4·row), and a lane reaches its half of a row's b limbs through
+// one buffer descriptor of kFoldSqLimbs/2 + 2 limb rows: folds past either limit stay on k_fold_unit
+constexpr size_t kFoldUnit1MaxRows = (size_t)1 << 30;
+constexpr size_t kFoldUnit1MaxStride = (((size_t)1 << 32) / (4 * (kFoldSqLimbs / 2 + 2)) - 1) / 64 * 64;
+size_t fold_unit1_min_rows(int cus);
+size_t fold_unit1_max_groups(int cus);
+hipError_t launch_fold_unit1(const uint32_t* D, size_t stride, size_t count, const uint32_t* sq, uint32_t k,
+                             uint32_t* Q, size_t qstride, size_t ngroups, hipStream_t st);
 // x1 <- x1 + x0·S (mod n, literal) in place: Q is then what launch_sq_join takes
 hipError_t launch_unit_join(uint32_t* Q, size_t qstride, size_t ngroups, const uint32_t* sq, uint32_t k,
                             hipStream_t st);

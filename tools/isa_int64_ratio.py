@@ -52,6 +52,8 @@ def compile_asm(src, out, hipcc=None, arch="gfx950"):
 
 def kernel_symbol(text, sub):
     names = [m for m in re.findall(r"^(_Z\w+):", text, re.M) if sub in m]
+    if len(names) > 1:  # k_fold_unit and k_fold_unit1: a whole identifier (length-prefixed when mangled) wins
+        names = [m for m in names if f"{len(sub)}{sub}" in m] or names
     if len(names) != 1:
         raise ValueError(f"{len(names)} kernels match {sub!r}: {names}")
     return names[0]
