@@ -1600,6 +1600,7 @@ int dds_ctx_reset_timing(dds_ctx* ctx) {
   std::lock_guard<std::mutex> lk(ctx->tmu);
   ctx->fold_ms = ctx->total_ms = 0;
   ctx->fold_launches = ctx->fold_modmuls = 0;
+  ctx->prime_ms[0] = ctx->prime_ms[1] = ctx->prime_ms[2] = 0;
   return DDS_OK;
 }
 

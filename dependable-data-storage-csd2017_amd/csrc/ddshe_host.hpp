@@ -1,5 +1,5 @@
 // Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp, ddshe_opecol.cpp,
-// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp):
+// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp):
 // contexts, stream/buffer pools, per-modulus Montgomery constants, device columns and the
 // orchestration helpers around the HIP kernels. Not part of the public ABI (include/ddshe.h).
 #pragma once
@@ -279,6 +279,11 @@ struct dds_ctx {
     bool owned = false;  // allocated by dds_host_alloc (hipHostFree), else registered caller memory
   };
   std::map<uintptr_t, HostReg> host_regs;
+  // prime search (ddshe_prime.cpp): the odd primes below 2^16, built and uploaded by the first call (under prmu)
+  std::mutex prmu;
+  ddshe::host::DevBuf prime_tab;
+  uint32_t prime_count = 0;
+  double prime_ms[3] = {0, 0, 0};  // timing on: device time of the sieves, base-2 passes, witness launches (under tmu)
   ~dds_ctx();
 };
 

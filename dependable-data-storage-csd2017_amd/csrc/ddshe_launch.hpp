@@ -1,5 +1,5 @@
 // Internal launcher interface between the C-ABI's host code (ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp,
-// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp) and the HIP kernels.
+// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -157,6 +157,21 @@ hipError_t launch_modexp1_pre(int S1, bool qp, const uint32_t* Xcol, size_t xstr
 hipError_t launch_modexp1_ladder(int S1, bool qp, const uint32_t* Tab, size_t tstride, size_t count,
                                  const uint32_t* c1, const uint32_t* sched, int nsched, uint32_t n0, uint32_t* O,
                                  size_t ostride, int S, hipStream_t st);
+// Prime search (ddshe_prime.hpp). launch_strong1: lane t < nlanes tests row idx[t / rounds] (t / rounds when idx is
+// null) of Ncol (S1 = 20 | 40 | 56 limbs of 28 bits, odd, >= 3, at most nbits <= 28 S1 - 2 bits each) to base 2
+// (base2), to row t of Bcol, or with Bcol null to the witness of (seed, row, t % rounds), N >= 5; out[t] = 1 iff
+// it is a strong probable prime to that base. launch_prime_sieve: flags[j * window + k] = 1 where an odd prime
+// of the table divides A_j + 2k without being it (flags zeroed by the caller). launch_prime_cands: row t of
+// Ncol = A_j + 2k for (j, k) = pairs[2t], pairs[2t + 1]. launch_prime_ingest: big-endian rows -> 28-bit limbs.
+hipError_t launch_strong1(int S1, bool base2, const uint32_t* Ncol, size_t nstride, const uint32_t* idx, size_t nlanes,
+                          uint32_t rounds, const uint32_t* Bcol, size_t bstride, uint64_t seed, int nbits, uint8_t* out,
+                          hipStream_t st);
+hipError_t launch_prime_sieve(const uint32_t* Acol, size_t astride, int nl, size_t nsearch, const uint32_t* primes,
+                              uint32_t nprimes, uint32_t window, uint8_t* flags, hipStream_t st);
+hipError_t launch_prime_cands(const uint32_t* Acol, size_t astride, int nl, const uint32_t* pairs, size_t ncand,
+                              uint32_t* Ncol, size_t nstride, int S, hipStream_t st);
+hipError_t launch_prime_ingest(const uint8_t* in, size_t width, size_t count, uint32_t* X, size_t stride, int S,
+                               hipStream_t st);
 // CRT encryption pieces (see ddshe_kernels.hip): radix change between rW layouts (flags[0] |= 1 on
 // overflow), h = (y_p - y_q)(q^2)^-1 mod p^2 (c12 = c1R | c2R, 2*S limbs), c = h*q^2 + y_q
 hipError_t launch_repack(const uint32_t* src, size_t sstride, int Ss, int Ws, uint32_t* dst, size_t dstride, int Sd,

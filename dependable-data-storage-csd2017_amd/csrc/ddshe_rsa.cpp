@@ -41,11 +41,13 @@ std::vector<uint8_t> be_of(const bn::Limbs& v) {
   return b;
 }
 
-// p, q as the C-ABI takes them: distinct, odd, > 1
+// p, q as the C-ABI takes them: distinct, odd, > 1. That is all this tests: the factors are NOT tested for
+// primality here (dds_probable_prime_batch does that; a composite factor that passes gives a wrong plaintext, or
+// DDS_E_ARG where an inverse the key needs does not exist)
 int check_factors(const bn::Limbs& p, const bn::Limbs& q) {
   if (p.empty() || q.empty() || !(p[0] & 1u) || !(q[0] & 1u) || bn::cmp(p, q) == 0 || bn::bit_length(p) < 2 ||
       bn::bit_length(q) < 2)
-    return fail(DDS_E_ARG, "p, q must be distinct odd primes");
+    return fail(DDS_E_ARG, "p, q must be distinct and odd, each above 1 (primality is not tested)");
   return DDS_OK;
 }
 

@@ -67,6 +67,8 @@ EXPORTS = [
     "dds_host_free", "dds_paillier_decrypt_batch_crt", "dds_col_decrypt_paillier",
     "dds_col_dec_width", "dds_col_read_dec", "dds_paillier_encrypt_batch_dec",
     "dds_rsa_decrypt_batch_crt", "dds_col_decrypt_rsa", "dds_rsa_crt_plan",
+    "dds_max_prime_bits", "dds_strong_probable_prime_batch", "dds_probable_prime_batch", "dds_next_prime_batch",
+    "dds_paillier_keygen_batch", "dds_rsa_keygen_batch", "dds_ctx_get_prime_timing",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -154,6 +156,16 @@ _sig("dds_rsa_decrypt_batch_crt", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char
 _sig("dds_col_decrypt_rsa", C.c_int, C.c_void_p, _sz, _sz, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz,
      _u8p, _sz)
 _sig("dds_rsa_crt_plan", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, C.POINTER(C.c_int), C.POINTER(C.c_int))
+_sig("dds_max_prime_bits", _sz)
+_sig("dds_strong_probable_prime_batch", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, _sz, _sz, _u8p)
+_sig("dds_probable_prime_batch", C.c_int, C.c_void_p, C.c_char_p, _sz, _sz, C.c_uint32, C.c_uint64, _u8p)
+_sig("dds_next_prime_batch", C.c_int, C.c_void_p, C.c_char_p, _sz, _sz, C.c_uint32, C.c_uint64, _sz, _u8p, _sz)
+_sig("dds_paillier_keygen_batch", C.c_int, C.c_void_p, _sz, C.c_uint64, C.c_uint64, _sz, C.c_uint32, _u8p, _u8p, _u8p,
+     _u8p, _u8p, _sz, _sz, _sz)
+_sig("dds_rsa_keygen_batch", C.c_int, C.c_void_p, _sz, C.c_char_p, _sz, C.c_uint64, C.c_uint64, _sz, C.c_uint32, _u8p,
+     _u8p, _u8p, _sz, _sz)
+_sig("dds_ctx_get_prime_timing", C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+     C.POINTER(C.c_double))
 _sig("dds_modexp_batch", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, C.c_char_p, _sz, _sz, _u8p)
 for _n in ("dds_sum_all_dec", "dds_mult_all_dec"):
     _sig(_n, C.c_int, C.c_void_p, C.POINTER(C.c_char_p), _sz, C.c_char_p, C.c_char_p, _sz, _szp)
@@ -553,6 +565,71 @@ class Engine:
         _check(_lib.dds_rsa_crt_plan(self._h, int_to_be(p, nbytes(p)), nbytes(p), int_to_be(q, nbytes(q)), nbytes(q),
                                      s1, qp), "dds_rsa_crt_plan")
         return ((s1[0], bool(qp[0])), (s1[1], bool(qp[1])))
+
+    # ---- prime search and key generation ----
+    @staticmethod
+    def _rows(buf, count: int, width: int) -> list[int]:
+        raw = bytes(buf)
+        return [int.from_bytes(raw[i * width:(i + 1) * width], "big") for i in range(count)]
+
+    def strong_probable_prime_batch(self, ns, bases) -> list[int]:
+        """flags[i] = 1 iff ns[i] (odd, >= 3) is a strong probable prime to bases[i] (in [1, ns[i] - 1])."""
+        ns, bases = [int(x) for x in ns], [int(x) for x in bases]
+        assert len(ns) == len(bases)
+        width = max([1] + [nbytes(x) for x in ns + bases])
+        flags = (C.c_uint8 * max(1, len(ns)))()
+        _check(_lib.dds_strong_probable_prime_batch(self._h, ints_to_be(ns, width), ints_to_be(bases, width), width,
+                                                    len(ns), flags), "dds_strong_probable_prime_batch")
+        return list(flags)[:len(ns)]
+
+    def probable_prime_batch(self, ns, rounds: int = 24, seed: int = 0) -> list[int]:
+        """flags[i] = 1 iff ns[i] >= 0 is a probable prime: base 2, then `rounds` seeded witnesses."""
+        ns = [int(x) for x in ns]
+        width = max([1] + [nbytes(x) for x in ns])
+        flags = (C.c_uint8 * max(1, len(ns)))()
+        _check(_lib.dds_probable_prime_batch(self._h, ints_to_be(ns, width), width, len(ns), rounds, seed, flags),
+               "dds_probable_prime_batch")
+        return list(flags)[:len(ns)]
+
+    def next_prime_batch(self, starts, rounds: int = 24, seed: int = 0, window: int = 0) -> list[int]:
+        """The smallest probable prime >= each start (window: odd candidates sieved per pass, 0: the default)."""
+        starts = [int(x) for x in starts]
+        width = max([1] + [nbytes(x) for x in starts])
+        ow = width + 1
+        out = (C.c_uint8 * (ow * max(1, len(starts))))()
+        _check(_lib.dds_next_prime_batch(self._h, ints_to_be(starts, width), width, len(starts), rounds, seed, window,
+                                         out, ow), "dds_next_prime_batch")
+        return self._rows(out, len(starts), ow)
+
+    def paillier_keygen_batch(self, bits: int, seed: int, count: int = 1, first: int = 0, rounds: int = 24) -> list[dict]:
+        """HomoAdd.generateKey for keys first .. first + count - 1 of (bits, seed): dicts with the fields of
+        tests/golden/keys.json (g, lambda, mu, n, nsquare, p, q)."""
+        fb, nb, gb = (bits + 15) // 16, (bits + 7) // 8, (bits + 3) // 4
+        m = max(1, count)
+        p, q, g = (C.c_uint8 * (fb * m))(), (C.c_uint8 * (fb * m))(), (C.c_uint8 * (gb * m))()
+        lam, mu = (C.c_uint8 * (nb * m))(), (C.c_uint8 * (nb * m))()
+        _check(_lib.dds_paillier_keygen_batch(self._h, bits, seed, first, count, rounds, p, q, g, lam, mu, fb, nb, gb),
+               "dds_paillier_keygen_batch")
+        cols = [self._rows(b, count, w) for b, w in ((p, fb), (q, fb), (g, gb), (lam, nb), (mu, nb))]
+        return [{"g": gi, "lambda": li, "mu": mi, "n": pi * qi, "nsquare": (pi * qi) ** 2, "p": pi, "q": qi}
+                for pi, qi, gi, li, mi in zip(*cols)]
+
+    def rsa_keygen_batch(self, bits: int, seed: int, count: int = 1, first: int = 0, rounds: int = 24,
+                         e: int = 65537) -> list[dict]:
+        """HomoMult.generateKey for keys first .. first + count - 1 of (bits, seed): dicts n, e, d, p, q."""
+        fb, nb = (bits + 15) // 16, (bits + 7) // 8
+        m = max(1, count)
+        p, q, d = (C.c_uint8 * (fb * m))(), (C.c_uint8 * (fb * m))(), (C.c_uint8 * (nb * m))()
+        _check(_lib.dds_rsa_keygen_batch(self._h, bits, int_to_be(e, nbytes(e)), nbytes(e), seed, first, count, rounds,
+                                         p, q, d, fb, nb), "dds_rsa_keygen_batch")
+        cols = [self._rows(b, count, w) for b, w in ((p, fb), (q, fb), (d, nb))]
+        return [{"n": pi * qi, "e": e, "d": di, "p": pi, "q": qi} for pi, qi, di in zip(*cols)]
+
+    def prime_timing(self) -> tuple:
+        """(sieve_ms, base2_ms, witness_ms) of the prime search since reset_timing(), with timing on."""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        _check(_lib.dds_ctx_get_prime_timing(self._h, C.byref(a), C.byref(b), C.byref(c)), "dds_ctx_get_prime_timing")
+        return a.value, b.value, c.value
 
     def modexp_batch(self, modulus: int, exponent: int, bases) -> list[int]:
         """out[i] = bases[i]^exponent mod modulus (HomoMult.encrypt for an RSA key)."""

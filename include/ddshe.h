@@ -489,6 +489,77 @@ int dds_col_decrypt_rsa(dds_col* col, size_t first, size_t count, const uint8_t*
 int dds_rsa_crt_plan(dds_ctx*, const uint8_t* p_be, size_t p_bytes, const uint8_t* q_be, size_t q_bytes, int s1[2],
                      int qp[2]);
 
+/* ---- prime search and key generation (HomoAdd.generateKey / HomoMult.generateKey,
+ * SJHomoLibProvider.scala:33-40) ------------------------------------------------------------
+ * All values big-endian in rows of the stated width. Every call is thread-safe on one context, runs on a
+ * stream of its pool, lets no exception cross, and with dds_ctx_set_timing on adds the device time of its
+ * kernels to total_ms (that of the strong-test launches also to fold_ms; the split by step:
+ * dds_ctx_get_prime_timing). The tests run one candidate per lane at 20, 40 or 56 limbs of 28 bits
+ * (N of up to 558, 1118, 1566 bits); rows of different lengths may share a call: all run in the class of
+ * the longest. */
+/* Largest N the prime tests take, in bits: 1566 (28 * 56 - 2, so that 4N <= 2^(28 * 56)). */
+size_t dds_max_prime_bits(void);
+/* BigInteger.isProbablePrime's building block, one Miller-Rabin round with a given base: flags[i] = 1 iff
+ * N_i is a strong probable prime to base b_i, i.e. with N_i - 1 = d 2^s, b^d == +-1 or b^(d 2^r) == -1
+ * (mod N_i) for some 0 < r < s. Rows of n_be and bases_be are `width` bytes. An N that is even or below 3, or
+ * a base outside [1, N - 1]: DDS_E_ARG; an N above dds_max_prime_bits(): DDS_E_UNSUPPORTED; both before any
+ * GPU work. */
+int dds_strong_probable_prime_batch(dds_ctx*, const uint8_t* n_be, const uint8_t* bases_be, size_t width, size_t count,
+                                    uint8_t* flags);
+/* BigInteger.isProbablePrime for `count` values N >= 0: flags[i] = 1 iff N_i is a probable prime. 0, 1 and
+ * even N > 2 answer 0, 2 and 3 answer 1, at ingress; every other N gets the strong test to base 2 and its
+ * survivors `rounds` (<= 65535) further strong tests, all rounds of all survivors as lanes of one launch. The
+ * witness of (seed, row i, round r) is uniform on [2, N - 2] by rejection: try j = 0, 1, ... draws limb l =
+ * splitmix64(splitmix64(seed ^ (i << 16 | r)) + 64 j + l) mod 2^28 for the 28-bit limbs of N, cut to
+ * bits(N) bits, and the first try inside the range is taken (each try succeeds with probability >= 1/4);
+ * after 256 failed tries (probability below 2^-106) the witness is 2. An odd N above dds_max_prime_bits():
+ * DDS_E_UNSUPPORTED before any GPU work. */
+int dds_probable_prime_batch(dds_ctx*, const uint8_t* n_be, size_t width, size_t count, uint32_t rounds, uint64_t seed,
+                             uint8_t* flags);
+/* BigInteger.nextProbablePrime, inclusive: out_j = the smallest probable prime >= start_j, for any start >= 0
+ * (rows of `width` bytes in, `out_width` bytes out). Starts up to 2 give 2, 3 gives 3; otherwise the
+ * candidates are c = start | 1, c + 2, ... Per pass every unfinished search sieves `window` odd candidates
+ * with the odd primes below 2^16 (one launch), all survivors of all searches get the base-2 test (one
+ * launch), and each search's smallest base-2 survivor gets `rounds` witness tests (one launch; witnesses as
+ * above with the survivor's index in the pass for the row); a search whose survivor fails moves to its next
+ * one, a search with no prime in the window to the next window. The result does not depend on `window`.
+ * window = 0 selects the default: twice the bit length of the longest start, rounded up to a multiple of
+ * 64, at least 64. Primes near 2^b have density 2 / (b ln 2) among odd numbers, so 2b odd candidates hold
+ * 5.8 primes on average and none with probability e^-5.8 = 0.3 %: nearly every search ends in its first
+ * pass; the sieve leaves 10.1 % of the candidates, 0.2 b base-2 lanes per search (104 at 512 bits, 207 at
+ * 1024), so a few hundred searches fill the device. window > 2^22: DDS_E_ARG. A search gives up after 2^22
+ * odd offsets: DDS_E_RANGE. A start above dds_max_prime_bits(), a window that reaches past it, or a result
+ * wider than out_width: DDS_E_RANGE. */
+int dds_next_prime_batch(dds_ctx*, const uint8_t* start_be, size_t width, size_t count, uint32_t rounds, uint64_t seed,
+                         size_t window, uint8_t* out_be, size_t out_width);
+/* HomoAdd.generateKey(bits) for keys i = first .. first + count - 1: a pure function of (bits, seed, i), whatever
+ * count, the window or the witnesses. The seed enters only as seed ^ tag, so the seeds s and s ^ x give the
+ * same streams under tags t and t ^ x (s and s ^ 1 swap p and q of attempt 0): distinct keys come from distinct
+ * i under one seed, or from seeds that differ above the tag bits in use. word(t, k) = low 32 bits of splitmix64(splitmix64(seed ^ t) + k);
+ * stream(t, b) = sum_k word(t, k) 2^(32 k) mod 2^b; draw(t, b) = stream(t, b) with bits b - 1, b - 2 and 0 set.
+ * Attempt a = 0, 1, ... of key i takes p = next_prime(draw((i << 16) | (a << 1), bits / 2)) and q the same with
+ * the low tag bit set (next_prime: dds_next_prime_batch with `rounds`), and is accepted iff both still have
+ * bits / 2 bits, p != q and gcd(n, (p - 1)(q - 1)) = 1, n = p q (which then has exactly `bits` bits). All
+ * primes of all keys of the call, and the retries of a pass, go through one search together. Then
+ * lambda = lcm(p - 1, q - 1); g = the first G_b = stream(2^63 | (i << 16) | b, 2 bits - 2), b = 0, 1, ..., with
+ * G_b >= 2, gcd(G_b, n) = 1 and L(G_b^lambda mod n^2) invertible mod n; mu = that inverse (per-key constants,
+ * computed on the host). Rows: p, q f_bytes each, lambda, mu n_bytes, g g_bytes. bits odd or below 64, rounds
+ * above 65535, first + count above 2^47: DDS_E_ARG; bits / 2 above dds_max_prime_bits() or n^2 above
+ * dds_max_modulus_bits(): DDS_E_UNSUPPORTED; rows too narrow (f_bytes < bits / 16, n_bytes < bits / 8,
+ * g_bytes < bits / 4): DDS_E_BUFSIZE; all before any GPU work. count == 0: DDS_OK. */
+int dds_paillier_keygen_batch(dds_ctx*, size_t bits, uint64_t seed, uint64_t first, size_t count, uint32_t rounds,
+                              uint8_t* p_out, uint8_t* q_out, uint8_t* g_out, uint8_t* lambda_out, uint8_t* mu_out,
+                              size_t f_bytes, size_t n_bytes, size_t g_bytes);
+/* HomoMult.generateKey(bits) with public exponent e (odd, >= 3: DDS_E_ARG otherwise): p and q drawn and searched
+ * exactly as above, an attempt accepted iff both have bits / 2 bits, p != q and gcd(e, (p - 1)(q - 1)) = 1;
+ * d = e^-1 mod (p - 1)(q - 1). Rows: p, q f_bytes each, d n_bytes. Errors as above, with n in place of n^2. */
+int dds_rsa_keygen_batch(dds_ctx*, size_t bits, const uint8_t* e_be, size_t e_bytes, uint64_t seed, uint64_t first,
+                         size_t count, uint32_t rounds, uint8_t* p_out, uint8_t* q_out, uint8_t* d_out, size_t f_bytes,
+                         size_t n_bytes);
+/* Device time, since dds_ctx_reset_timing, of the prime search's sieve launches, base-2 launches and witness
+ * launches (ms; accumulated while dds_ctx_set_timing is on). */
+int dds_ctx_get_prime_timing(dds_ctx*, double* sieve_ms, double* base2_ms, double* witness_ms);
+
 /* Batched modular exponentiation out[i] = base[i]^exp mod modulus (mod_bytes each):
  * HomoMult.encrypt(pk, m) = m^e mod n (SJHomoLibProvider.scala:59) and decrypt-side
  * checks. Bases are validated like fold operands. */
