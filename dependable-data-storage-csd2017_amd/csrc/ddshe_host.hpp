@@ -1,5 +1,5 @@
 // Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp, ddshe_opecol.cpp,
-// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp):
+// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp):
 // contexts, stream/buffer pools, per-modulus Montgomery constants, device columns and the
 // orchestration helpers around the HIP kernels. Not part of the public ABI (include/ddshe.h).
 #pragma once
@@ -101,6 +101,10 @@ struct Worker {
   DevBuf sflags;            // string scans' row flags, zero between scans when sflags_zero
   bool sflags_zero = false;
   hipEvent_t ev_done = {};
+  DevBuf exps;               // per-row exponent ladder: the call's exponents (uint64)
+  // weighted fold: weights (int64), the call's row ids, block histograms, bucket sizes, the bucket list (its own
+  // id buffer: the fold it feeds uses `ids` for live ranges)
+  DevBuf wf_w, wf_ids, wf_hist, wf_cnt, wf_list;
   DevBuf crt[7];  // CRT scratch of Paillier encryption and decryption (encrypt_crt_device, decrypt_crt_device)
   hipEvent_t ev[4] = {};
   // decimal codec: double-buffered pinned chunks (chars, offsets), their device copies,
@@ -616,6 +620,11 @@ int modmul_fold_be(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, size_t
 // rW, fully normalised, < 2N (ddshe_paillier.cpp). Synchronises the stream.
 int modexp_device(Worker* w, hipStream_t st, ModConsts& mc, const bn::Limbs& E, const bn::Limbs* g, const uint32_t* d_x,
                   size_t xstride, const uint32_t* d_m, size_t count, uint32_t* d_out, size_t ostride);
+// out[i] = x[i]^e[i] mod N on the device with the per-row ladder (ddshe_linear.cpp): d_exps holds the `count`
+// exponents (device, uint64), max_bits the bit length of the largest. x rows as above. Synchronises the stream.
+// With the context's timing on, the kernels' device time goes to total_ms and the ladders' to fold_ms.
+int exprows_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* d_x, size_t xstride,
+                   const uint64_t* d_exps, size_t max_bits, size_t count, uint32_t* d_out, size_t ostride);
 int product_tree(dds_ctx* ctx, const std::vector<uint32_t>& h, size_t count, size_t len, size_t cap16, bn::Limbs* out);
 int fold_even_modulus(dds_ctx* ctx, const bn::Limbs& M, const std::vector<bn::Limbs>& xs, const std::vector<bool>& negs,
                       bn::Limbs* out);

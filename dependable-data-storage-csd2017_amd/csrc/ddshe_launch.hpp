@@ -1,5 +1,6 @@
 // Internal launcher interface between the C-ABI's host code (ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp,
-// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp) and the HIP kernels.
+// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp) and the
+// HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -157,6 +158,24 @@ hipError_t launch_modexp1_pre(int S1, bool qp, const uint32_t* Xcol, size_t xstr
 hipError_t launch_modexp1_ladder(int S1, bool qp, const uint32_t* Tab, size_t tstride, size_t count,
                                  const uint32_t* c1, const uint32_t* sched, int nsched, uint32_t n0, uint32_t* O,
                                  size_t ostride, int S, hipStream_t st);
+// Per-row exponent ladder (ddshe_exprows.hpp): O[i] = x_i^(exps[i]) mod N at the fixed window w (1..4) over ndig
+// digits. Tab: S limb rows of stride 2^w * chunk, entry j of row r in column j * chunk + r (count <= chunk,
+// PF * 2^w * chunk * 4 < 2^32: the launchers refuse anything else).
+hipError_t launch_exprows_pre(int S, const uint32_t* Xcol, size_t xstride, size_t count, const uint32_t* consts,
+                              const uint32_t* qp_mod, uint32_t n0, int w, uint32_t* Tab, size_t chunk,
+                              hipStream_t st);
+hipError_t launch_exprows_ladder(int S, const uint32_t* Tab, size_t chunk, const uint64_t* exps, size_t count,
+                                 const uint32_t* consts, const uint32_t* qp_mod, int w, int ndig, uint32_t n0,
+                                 uint32_t* O, size_t ostride, hipStream_t st);
+// Weighted fold (ddshe_wfold.hip): the rows of items [0, n) (ids[i], or first + i when ids is null) whose weight
+// has the sign asked for, whose row is live (live[row] != 0, or live null) and whose digit
+// d = (|weight| >> shift) & (2^cbits - 1) is not 0, grouped by d: counts[d] (kWfoldBuckets words) and the row
+// ids of bucket 1, then 2, ... back to back in list (n words). hist: kWfoldBuckets * wfold_blocks(n) words.
+constexpr int kWfoldBuckets = 256;
+size_t wfold_blocks(size_t n);
+hipError_t launch_wfold_buckets(const int64_t* weights, const uint32_t* ids, uint32_t first, const uint8_t* live,
+                                size_t n, bool neg, uint32_t shift, int cbits, uint32_t* hist, uint32_t* counts,
+                                uint32_t* list, hipStream_t st);
 // Prime search (ddshe_prime.hpp). launch_strong1: lane t < nlanes tests row idx[t / rounds] (t / rounds when idx is
 // null) of Ncol (S1 = 20 | 40 | 56 limbs of 28 bits, odd, >= 3, at most nbits <= 28 S1 - 2 bits each) to base 2
 // (base2), to row t of Bcol, or with Bcol null to the witness of (seed, row, t % rounds), N >= 5; out[t] = 1 iff

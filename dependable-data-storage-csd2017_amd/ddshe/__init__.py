@@ -69,6 +69,8 @@ EXPORTS = [
     "dds_rsa_decrypt_batch_crt", "dds_col_decrypt_rsa", "dds_rsa_crt_plan",
     "dds_max_prime_bits", "dds_strong_probable_prime_batch", "dds_probable_prime_batch", "dds_next_prime_batch",
     "dds_paillier_keygen_batch", "dds_rsa_keygen_batch", "dds_ctx_get_prime_timing",
+    "dds_modexp_rows", "dds_col_append_pow", "dds_exprows_plan", "dds_col_fold_weighted",
+    "dds_col_fold_weighted_dec", "dds_fold_weighted_plan",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -170,6 +172,13 @@ _sig("dds_modexp_batch", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, 
 for _n in ("dds_sum_all_dec", "dds_mult_all_dec"):
     _sig(_n, C.c_int, C.c_void_p, C.POINTER(C.c_char_p), _sz, C.c_char_p, C.c_char_p, _sz, _szp)
 _u64p = C.POINTER(C.c_uint64)
+_i64p = C.POINTER(C.c_int64)
+_sig("dds_modexp_rows", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, _u64p, _sz, _u8p)
+_sig("dds_col_append_pow", C.c_int, C.c_void_p, C.c_void_p, _sz, _sz, _u64p)
+_sig("dds_exprows_plan", C.c_int, _sz, C.POINTER(C.c_int), _u64p)
+_sig("dds_col_fold_weighted", C.c_int, C.c_void_p, _u64p, _sz, _sz, _i64p, _sz, _u8p, _sz, _szp)
+_sig("dds_col_fold_weighted_dec", C.c_int, C.c_void_p, _u64p, _sz, _sz, _i64p, _sz, C.c_char_p, _sz, _szp)
+_sig("dds_fold_weighted_plan", C.c_int, _sz, _sz, _sz, C.POINTER(C.c_int), _u64p, _u64p)
 _sig("dds_pair_modmul_dec", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _sz, _szp)
 _sig("dds_pair_stats", C.c_int, C.c_void_p, _u64p, _u64p)
 _sig("dds_pair_timing", C.c_int, C.c_void_p, _u64p, _u64p, _u64p, _u64p)
@@ -259,6 +268,13 @@ def _split_dec(chars: np.ndarray, offs: np.ndarray) -> list[str]:
 
 def _ids(row_ids) -> np.ndarray:
     return np.ascontiguousarray(row_ids, dtype=np.uint64)
+
+
+def _u64_array(xs) -> np.ndarray:
+    """Exponents below 2^64 as a contiguous uint64 array (an array of that type is taken as it is)."""
+    if isinstance(xs, np.ndarray) and xs.dtype == np.uint64:
+        return np.ascontiguousarray(xs)
+    return np.ascontiguousarray([int(x) for x in xs], dtype=np.uint64)
 
 
 def _dec_rows(rows):
@@ -643,6 +659,38 @@ class Engine:
         raw = bytes(out)
         return [int.from_bytes(raw[i * mb:(i + 1) * mb], "big") for i in range(len(bases))]
 
+    def modexp_rows(self, modulus: int, bases, exps) -> list[int]:
+        """dds_modexp_rows: out[i] = bases[i]^exps[i] mod modulus, an exponent below 2^64 of its own per row
+        (Paillier's scalar multiple Enc(k m) = c^k mod n^2)."""
+        bases = [int(x) for x in bases]
+        e = _u64_array(exps)
+        if len(e) != len(bases):
+            raise ValueError("one exponent per base")
+        mb = nbytes(modulus)
+        width = max([mb] + [nbytes(x) for x in bases])
+        out = (C.c_uint8 * (mb * max(1, len(bases))))()
+        _check(_lib.dds_modexp_rows(self._h, int_to_be(modulus, mb), mb, ints_to_be(bases, width), width,
+                                    e.ctypes.data_as(_u64p), len(bases), out), "dds_modexp_rows")
+        raw = bytes(out)
+        return [int.from_bytes(raw[i * mb:(i + 1) * mb], "big") for i in range(len(bases))]
+
+    @staticmethod
+    def exprows_plan(bits: int) -> tuple:
+        """dds_exprows_plan: (window, Montgomery products per row) of a per-row ladder call whose largest
+        exponent has `bits` bits. No GPU work."""
+        w, p = C.c_int(), C.c_uint64()
+        _check(_lib.dds_exprows_plan(bits, C.byref(w), C.byref(p)), "dds_exprows_plan")
+        return w.value, p.value
+
+    @staticmethod
+    def fold_weighted_plan(rows: int, bits: int, window: int = 0) -> tuple:
+        """dds_fold_weighted_plan: (window, fold products, host products) the weighted fold's plan predicts for
+        `rows` rows and weights of up to `bits` bits (window 0: the default). No GPU work."""
+        c, rp, hp = C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(_lib.dds_fold_weighted_plan(rows, bits, window, C.byref(c), C.byref(rp), C.byref(hp)),
+               "dds_fold_weighted_plan")
+        return c.value, rp.value, hp.value
+
     def host_register(self, arr: np.ndarray):
         """dds_host_register: page-lock a reusable output array (results DMA'd straight into it)."""
         _check(_lib.dds_host_register(self._h, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "dds_host_register")
@@ -818,6 +866,52 @@ class Column(_Mutable):
         olen = C.c_size_t()
         _check(_lib.dds_col_fold_dec(self._h, None if ids is None else ids.ctypes.data_as(_u64p), n, out, cap,
                                      C.byref(olen)), "dds_col_fold_dec")
+        return out.value.decode()
+
+    def append_pow(self, src: "Column", first: int, count: int, exps):
+        """dds_col_append_pow: append rows [first, first+count) of src, each raised to its own exponent
+        exps[i] < 2^64 (Enc(k_i m_i) for a Paillier column)."""
+        e = _u64_array(exps)
+        if len(e) != count:
+            raise ValueError("one exponent per row")
+        _check(_lib.dds_col_append_pow(self._h, src._h, first, count, e.ctypes.data_as(_u64p)), "dds_col_append_pow")
+
+    def _weighted_args(self, weights, row_ids, first, count):
+        if isinstance(weights, np.ndarray) and weights.dtype == np.int64:
+            wts = np.ascontiguousarray(weights)
+        else:
+            wts = np.ascontiguousarray([int(x) for x in weights], dtype=np.int64)
+        if row_ids is None:
+            ids, n = None, len(self) - first if count is None else count
+        else:
+            ids = np.ascontiguousarray(row_ids, dtype=np.uint64)
+            n = len(ids)
+        if len(wts) != n:
+            raise ValueError("one weight per listed row")
+        return wts, ids, n
+
+    def fold_weighted(self, weights, row_ids=None, first: int = 0, count: int | None = None, window: int = 0) -> int:
+        """dds_col_fold_weighted: prod c_i^(w_i) mod N (Enc(sum w_i m_i) for a Paillier column) over the live
+        rows among row_ids (or rows [first, first+count)), signed 64-bit weights, weights[i] for the i-th listed
+        row. window: bits of the bucket digits, 1..8 (0: the plan's default); the value does not depend on it."""
+        wts, ids, n = self._weighted_args(weights, row_ids, first, count)
+        out = (C.c_uint8 * self.mb)()
+        olen = C.c_size_t()
+        _check(_lib.dds_col_fold_weighted(self._h, None if ids is None else ids.ctypes.data_as(_u64p), first, n,
+                                          wts.ctypes.data_as(_i64p), window, out, len(out), C.byref(olen)),
+               "dds_col_fold_weighted")
+        return _be_int(out, olen.value)
+
+    def fold_weighted_dec(self, weights, row_ids=None, first: int = 0, count: int | None = None,
+                          window: int = 0) -> str:
+        """dds_col_fold_weighted_dec: the same value as the route's decimal reply."""
+        wts, ids, n = self._weighted_args(weights, row_ids, first, count)
+        cap = 4 * self.mb + 64
+        out = C.create_string_buffer(cap)
+        olen = C.c_size_t()
+        _check(_lib.dds_col_fold_weighted_dec(self._h, None if ids is None else ids.ctypes.data_as(_u64p), first, n,
+                                              wts.ctypes.data_as(_i64p), window, out, cap, C.byref(olen)),
+               "dds_col_fold_weighted_dec")
         return out.value.decode()
 
     def fold_partial_device(self, d_partial: int, first: int = 0, count: int | None = None):

@@ -566,6 +566,41 @@ int dds_ctx_get_prime_timing(dds_ctx*, double* sieve_ms, double* base2_ms, doubl
 int dds_modexp_batch(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, const uint8_t* exp_be, size_t exp_bytes,
                      const uint8_t* bases_be, size_t width, size_t count, uint8_t* out);
 
+/* ---- Paillier's linear algebra: scalar multiples and the weighted SumAll ----------
+ * Enc(k m) = c^k mod n^2 with an exponent of its own per row (a fixed-window ladder over a per-row table of
+ * consecutive powers, window 1..4 from the call's largest exponent), and Enc(sum w_i m_i) = prod c_i^(w_i)
+ * mod n^2 over a resident column with signed 64-bit weights (bucket method: per window of c bits the rows are
+ * grouped by digit on the GPU, each bucket is folded by the gather fold, and the host combines the buckets, the
+ * windows and the two signs, with one modular inverse). Every call is thread-safe on one context, runs on a stream
+ * of its pool and lets no exception cross. With dds_ctx_set_timing on, the two ladder calls add their kernels'
+ * device time to total_ms and the ladders' to fold_ms; the weighted fold adds its grouping kernels' to total_ms
+ * and its folds' to fold_ms. */
+/* out[i] = bases[i]^exps[i] mod N, BigInteger.modPow per row (x^0 = 1 mod N, including 0^0). Bases validated like
+ * fold operands (>= N: DDS_E_RANGE). N even or < 3: DDS_E_ARG. All before any GPU work. count == 0: DDS_OK. */
+int dds_modexp_rows(dds_ctx*, const uint8_t* mod_be, size_t mod_bytes, const uint8_t* bases_be, size_t width,
+                    const uint64_t* exps, size_t count, uint8_t* out);
+/* Enc(k_i * m_i): append rows [first, first+count) of `in`, each raised to exps[i], to `out`. Both columns are over the
+ * same modulus; positional like dds_col_read. Another modulus, rows past the end, or out == in: DDS_E_ARG before
+ * any GPU work. */
+int dds_col_append_pow(dds_col* out, dds_col* in, size_t first, size_t count, const uint64_t* exps);
+/* Which window and how many Montgomery products per row a call whose largest exponent has max_bits bits gets.
+ * No GPU work. */
+int dds_exprows_plan(size_t max_bits, int* window, uint64_t* products_per_row);
+/* Enc(sum w_i m_i) = prod c_i^(w_i) mod N over the live rows among row_ids[0..n) (NULL: rows [first, first+n)), weights[i]
+ * belonging to the i-th of them; a row id listed twice contributes both terms. weights[i] goes with the i-th
+ * listed row (row_ids[i], or row first + i), dead rows drop out together with their weights. window: the bucket
+ * digits' bits, 1..8, or 0 for the plan's default (> 8: DDS_E_ARG); the value does not depend on it. The value is
+ * always the canonical residue (also for a single row of weight 1). No live row: DDS_E_EMPTY. Every weight 0:
+ * the value 1. A row of negative weight that is no unit mod N: DDS_E_RANGE. INT64_MIN is a legal weight. */
+int dds_col_fold_weighted(dds_col*, const uint64_t* row_ids, size_t first, size_t n, const int64_t* weights,
+                          size_t window, uint8_t* out, size_t out_cap, size_t* out_len);
+/* The same as the route's decimal reply (like dds_col_fold_dec). */
+int dds_col_fold_weighted_dec(dds_col*, const uint64_t* row_ids, size_t first, size_t n, const int64_t* weights,
+                              size_t window, char* out, size_t out_cap, size_t* out_len);
+/* The default window and the number of fold products + host products the plan predicts. No GPU work. */
+int dds_fold_weighted_plan(size_t rows, size_t max_bits, size_t window_in, int* window, uint64_t* row_products,
+                           uint64_t* host_products);
+
 /* ---- device-resident batched encryption (BASELINE.json config 4) --------------
  * dds_col_fill_random: append `count` seeded random rows r < 2^bits (odd, so r != 0):
  *   limb l of row i = splitmix64(splitmix64(seed ^ (row0+i)) + l) in the column's rW layout.
