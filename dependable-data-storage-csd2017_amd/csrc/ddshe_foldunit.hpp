@@ -98,7 +98,7 @@ struct MontUnit {
   static_assert((2ull * (S - 2 * TPI) + 3ull * 2 * TPI + 2) < (1ull << (64 - 2 * W)), "chain B lazy 64-bit bound");
   // S = Σ b in 32-bit limbs: every b limb is < 2^W, a carry pass (carry) leaves a limb below 2^W + 2^(32-W),
   // and at most kSumRows rows are added between two passes
-  static constexpr int kSumRows = 8;
+  static constexpr int kSumRows = kFoldUnitSumRows;
   static_assert(((uint64_t)(kSumRows + 1) << W) + (1ull << (32 - W)) <= (1ull << 32), "S limbs stay in 32 bits");
 
   // MontSq::step without the x0[l]·y1 mads

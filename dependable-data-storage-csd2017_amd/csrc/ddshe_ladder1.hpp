@@ -36,11 +36,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ddshe_consts.hpp"  // kL1*
 #include "ddshe_fold.hpp"
 
 namespace ddshe {
 
-enum { kL1Mod = 0, kL1N = 1, kL1Rmod = 2, kL1R2 = 3, kL1Count = 4 };
 constexpr int kLadder1Lanes = 64;  // one wave per workgroup: a slot column is 64 dwords
 
 template <int S1, int W, bool QP>

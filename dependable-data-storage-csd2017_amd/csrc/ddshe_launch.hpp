@@ -6,12 +6,11 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "ddshe_consts.hpp"  // kConst*, kFoldSq*, kSq*, kInv*, kFoldUnit*: the numbers shared with the CPU checks
+
 namespace ddshe {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));  // 16-byte vector loads
-
-// per-modulus constant block: 5 vectors of S r27 limbs each
-enum { kConstN = 0, kConstRmod = 1, kConstR2 = 2, kConstOne = 3, kConstN2x = 4, kConstCount = 5 };
 
 struct Shape {
   int S;    // limbs
@@ -48,12 +47,9 @@ hipError_t launch_fold(int S, const uint32_t* X, size_t xstride, size_t count, c
                        const uint32_t* ids = nullptr,  // ids: fold rows ids[0..count) (device, u32)
                        int lane1 = 0);  // != 0: one bignum per lane (k_fold1) at lane1 = fold1_limbs(S, bits) limbs
 // Digit-form fold of a perfect-square modulus n² in the (148, 4, 28) shape (ddshe_foldsq.hpp): values as
-// two base-n digits of kFoldSqLimbs limbs each. sq: kSqCount vectors of kFoldSqLimbs limbs (ñ = k·n | n |
-// C | R mod n | R² mod n), k = -n⁻¹ mod 2^28. The mirror D and the digit partials Q are limb-major, 2·kFoldSqLimbs
-// limb rows (digit 0, then digit 1). DDSHE_FOLD_SQ=0 disables the path, DDSHE_FOLD_SQ_MIN=<rows>
-// overrides the row count from which a fold takes it.
-constexpr int kFoldSqLimbs = 76, kFoldSqWide = 148;
-enum { kSqNq = 0, kSqN = 1, kSqC = 2, kSqRmod = 3, kSqR2 = 4, kSqCount = 5 };  // kSqR2: R² mod n
+// two base-n digits of kFoldSqLimbs limbs each. sq: the kSq* block of ddshe_consts.hpp, k = -n⁻¹ mod 2^28. The
+// mirror D and the digit partials Q are limb-major, 2·kFoldSqLimbs limb rows (digit 0, then digit 1).
+// DDSHE_FOLD_SQ=0 disables the path, DDSHE_FOLD_SQ_MIN=<rows> overrides the row count from which a fold takes it.
 bool fold_sq_enabled();
 size_t fold_sq_min_rows(int cus);
 size_t fold_sq_max_groups(int cus);
@@ -68,12 +64,6 @@ hipError_t launch_sq_join(const uint32_t* Q, size_t qstride, size_t ngroups, con
 // the fold multiplies by the one digit w and sums the b. DDSHE_FOLD_UNIT_AFTER=<h>: a column enters it at
 // its h-th mirror hit (default 2, 0: never).
 int fold_unit_after();
-// rows per group of one inversion level, and the row count at or below which the host finishes
-constexpr size_t kInvFan = 32;
-// rows whose prefix products one upgrade pass holds in scratch (kFoldSqLimbs limbs each)
-constexpr size_t kInvChunkRows = (size_t)1 << 20;
-// rows per group k_fold_unit admits: the sum of the b stays below R
-constexpr size_t kFoldUnitMaxRowsPerGroup = (size_t)1 << 26;
 // Up pass of a batch inversion mod n over rows [0, count) of the digit plane Wp: Pfx[., row] = the product
 // of the group's rows before `row` (times R, Montgomery), T[., g] = the group's total. Group g: rows g, g + G, ...
 hipError_t launch_inv_up(const uint32_t* Wp, size_t wstride, size_t count, const uint32_t* sq, uint32_t k,
@@ -89,7 +79,6 @@ hipError_t launch_fold_unit(const uint32_t* D, size_t stride, size_t count, cons
 // The same fold at one chain per lane (ddshe_foldunit1.hpp: a pair of lanes per group, S in LDS), same Q.
 // Taken from fold_unit1_min_rows rows upwards (DDSHE_FOLD_UNIT1=0 disables it, DDSHE_FOLD_UNIT1_MIN=<rows>
 // overrides), with up to fold_unit1_max_groups pairs.
-constexpr size_t kFoldUnit1RowsPerPair = 16;
 // its row loop runs on 32-bit byte offsets (4·row), and a lane reaches its half of a row's b limbs through
 // one buffer descriptor of kFoldSqLimbs/2 + 2 limb rows: folds past either limit stay on k_fold_unit
 constexpr size_t kFoldUnit1MaxRows = (size_t)1 << 30;

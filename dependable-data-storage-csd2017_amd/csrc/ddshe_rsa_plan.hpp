@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "bn_host.hpp"
+#include "ddshe_consts.hpp"
 
 namespace ddshe {
 namespace host {
@@ -33,11 +34,15 @@ inline bn::Limbs rsa_crt_exponent(const bn::Limbs& d, const bn::Limbs& f) {
 inline std::vector<uint32_t> ladder1_consts(const bn::Limbs& N, int S1, int W, bool qp, uint32_t* n0) {
   *n0 = bn::mont_n0(N[0], W);
   const bn::Limbs r1 = bn::mod(bn::pow2((size_t)W * S1), N);
-  std::vector<uint32_t> out;
-  for (const bn::Limbs& v : {qp ? bn::mul(N, bn::Limbs{*n0}) : N, N, r1, bn::mulmod(r1, r1, N)}) {
+  std::vector<uint32_t> out((size_t)kL1Count * S1);
+  auto put = [&](int slot, const bn::Limbs& v) {
     const std::vector<uint32_t> r = bn::to_rw(v, S1, W);
-    out.insert(out.end(), r.begin(), r.end());
-  }
+    std::copy(r.begin(), r.end(), out.begin() + (size_t)slot * S1);
+  };
+  put(kL1Mod, qp ? bn::mul(N, bn::Limbs{*n0}) : N);
+  put(kL1N, N);
+  put(kL1Rmod, r1);
+  put(kL1R2, bn::mulmod(r1, r1, N));
   return out;
 }
 

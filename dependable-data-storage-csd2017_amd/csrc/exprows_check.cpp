@@ -6,26 +6,21 @@
 // 2^32 extent of one buffer descriptor; the bucket digits are recombined into |w|; and the bucket method
 // (running-product combine, Horner step, sign split, final inverse) is compared with the product of bn::powmod
 // terms. Exits non-zero on the first failed check, naming it; prints "ok <case>" lines and
-// "exprows_check: all passed" (tests/test_exprows_check.py).
+// "exprows_check: all passed" (tests/test_cpu_checks.py).
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "bn_host.hpp"
+#include "check_util.hpp"
 #include "ddshe_exprows_plan.hpp"
 #include "ddshe_wfold_plan.hpp"
 
 using namespace ddshe;
 using namespace ddshe::host;
+using ddshe::check::die;
 
 namespace {
-
-[[noreturn]] void die(const std::string& what) {
-  std::printf("FAIL: %s\n", what.c_str());
-  std::fflush(stdout);
-  std::exit(1);
-}
 
 uint64_t g_seed = 0x243F6A8885A308D3ull;
 uint64_t rnd() {  // a fixed 64-bit LCG (Knuth's MMIX constants), high bits mixed down
@@ -98,13 +93,13 @@ void check_plans() {
   for (size_t B = 0; B <= 64; ++B) {
     int best = 0;
     uint64_t bc = 0;
-    for (int w = 1; w <= 4; ++w) {
+    for (int w = 1; w <= kExprowsMaxWindow; ++w) {
       const uint64_t cost = (uint64_t)((B + w - 1) / w) * (w + 1) + ((uint64_t)1 << w) - 2;
       if (!best || cost < bc) best = w, bc = cost;
     }
     uint64_t p = 0;
     if (exprows_window(B, &p) != best || p != bc) die("exprows plan B=" + std::to_string(B));
-    for (int w = 1; w <= 4; ++w)
+    for (int w = 1; w <= kExprowsMaxWindow; ++w)
       if (B && (exprows_digits(B, w) - 1) * (size_t)w > 63) die("digit shift past 63 bits");
   }
   // B = 64 is a tie between w = 3 and w = 4 (94 products each): the smaller window wins
@@ -115,13 +110,13 @@ void check_plans() {
     for (size_t B = 0; B <= 64; ++B) {
       int best = 0;
       uint64_t bc = 0;
-      for (int c = 1; c <= 8; ++c) {
+      for (int c = 1; c <= kWfoldMaxWindow; ++c) {
         const uint64_t cost = (uint64_t)((B + c - 1) / c) * ((uint64_t)r + ((uint64_t)1 << (c + 1)));
         if (!best || cost < bc) best = c, bc = cost;
       }
       if (wfold_window(r, B, 0) != best) die("wfold plan rows=" + std::to_string(r) + " B=" + std::to_string(B));
       if (wfold_row_products(r, B, best) + wfold_host_products(B, best) != bc) die("wfold plan products");
-      for (size_t c = 1; c <= 8; ++c)
+      for (size_t c = 1; c <= (size_t)kWfoldMaxWindow; ++c)
         if (wfold_window(r, B, c) != (int)c) die("wfold plan: a given window is kept");
     }
   std::printf("ok window plans (exponent bits 0..64, %zu row counts)\n", sizeof(rows) / sizeof(rows[0]));
@@ -130,7 +125,7 @@ void check_plans() {
 void check_columns() {
   size_t n = 0;
   for (int S : {40, 76, 112, 148, 232, 320, 640})
-    for (int w = 1; w <= 4; ++w) {
+    for (int w = 1; w <= kExprowsMaxWindow; ++w) {
       const uint64_t pf = (S % 4 == 0) ? 4 : 2;
       for (size_t chunk : {(size_t)64, (size_t)128, (size_t)65536}) {
         const size_t stride = exprows_stride(w, chunk);

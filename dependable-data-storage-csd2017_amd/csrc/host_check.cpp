@@ -3,66 +3,19 @@
 // the first failed check, naming it; prints one line "E_hex squarings multiplies" per exponent
 // (tests/test_host_helpers.py compares them with bench.py's window_counts).
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "bn_host.hpp"
+#include "check_util.hpp"
 #include "ddshe_window.hpp"
 
 using namespace ddshe;
+using namespace ddshe::check;
 
 namespace {
 
-[[noreturn]] void die(const std::string& what) {
-  std::printf("FAIL: %s\n", what.c_str());
-  std::fflush(stdout);
-  std::exit(1);
-}
-
-bn::Limbs from_hex(const char* s) {
-  bn::Limbs r;
-  size_t n = 0;
-  while (s[n]) ++n;
-  for (size_t i = 0; i < n; ++i) {
-    const char c = s[n - 1 - i];
-    const uint32_t d = c <= '9' ? c - '0' : (c | 0x20) - 'a' + 10;
-    if (i / 8 >= r.size()) r.push_back(0);
-    r[i / 8] |= d << (4 * (i % 8));
-  }
-  bn::trim(r);
-  return r;
-}
-
-std::string to_hex(const bn::Limbs& a) {
-  if (a.empty()) return "0";
-  std::string s;
-  char buf[16];
-  std::snprintf(buf, sizeof buf, "%x", a.back());
-  s += buf;
-  for (size_t i = a.size() - 1; i-- > 0;) {
-    std::snprintf(buf, sizeof buf, "%08x", a[i]);
-    s += buf;
-  }
-  return s;
-}
-
-// an odd value of exactly `bits` bits from a fixed 64-bit LCG (Knuth's MMIX constants)
-bn::Limbs lcg_odd(size_t bits, uint64_t seed) {
-  bn::Limbs r((bits + 31) / 32);
-  for (auto& w : r) {
-    seed = seed * 6364136223846793005ull + 1442695040888963407ull;
-    w = (uint32_t)(seed >> 32);
-  }
-  r = bn::low_bits(r, bits);
-  r.resize((bits + 31) / 32, 0);
-  r[(bits - 1) / 32] |= 1u << ((bits - 1) % 32);
-  r[0] |= 1u;
-  return r;
-}
-
 bn::Limbs shl(const bn::Limbs& a, size_t k) { return bn::mul(a, bn::pow2(k)); }
-bn::Limbs pow2m1(size_t k) { return bn::sub(bn::pow2(k), bn::Limbs{1}); }
 
 void check_inv_mod_pow2() {
   const bn::Limbs mods[] = {{1}, {3}, {0xFFFFFFFFu}, lcg_odd(2048, 1), lcg_odd(3071, 2)};

@@ -1,58 +1,25 @@
 // CPU check of the one-bignum-per-lane modexp ladder (ddshe_ladder1.hpp) and of the host arithmetic of RSA-CRT
 // decryption (ddshe_rsa_plan.hpp). No HIP. The kernels' arithmetic is restated limb by limb: Mont1::step and
-// settle (ddshe_fold.hpp) with every lazy 64-bit sum checked against 2^64, Lad1::mul's order of steps, and
+// settle with every lazy 64-bit sum checked against 2^64 and Lad1::mul's order of steps (check_mont1.hpp), and
 // k_modexp1_pre / k_modexp1_ladder's order of products over window_schedule's output (table of odd powers,
 // leading window, squarings and window multiplies, the product by 1 against N, the canonical subtraction),
 // compared with bn::powmod. Exits non-zero on the first failed check, naming it; prints "ok <case>" lines and
-// "ladder1_check: all passed" (tests/test_ladder1_check.py).
+// "ladder1_check: all passed" (tests/test_cpu_checks.py).
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "bn_host.hpp"
+#include "check_mont1.hpp"
+#include "check_util.hpp"
+#include "ddshe_consts.hpp"
 #include "ddshe_rsa_plan.hpp"
 #include "ddshe_window.hpp"
 
 using namespace ddshe;
+using namespace ddshe::check;
 
 namespace {
-
-[[noreturn]] void die(const std::string& what) {
-  std::printf("FAIL: %s\n", what.c_str());
-  std::fflush(stdout);
-  std::exit(1);
-}
-
-bn::Limbs from_hex(const char* s) {
-  bn::Limbs r;
-  size_t n = 0;
-  while (s[n]) ++n;
-  for (size_t i = 0; i < n; ++i) {
-    const char c = s[n - 1 - i];
-    const uint32_t d = c <= '9' ? c - '0' : (c | 0x20) - 'a' + 10;
-    if (i / 8 >= r.size()) r.push_back(0);
-    r[i / 8] |= d << (4 * (i % 8));
-  }
-  bn::trim(r);
-  return r;
-}
-
-// an odd value of exactly `bits` bits from a fixed 64-bit LCG (Knuth's MMIX constants)
-bn::Limbs lcg_odd(size_t bits, uint64_t seed) {
-  bn::Limbs r((bits + 31) / 32);
-  for (auto& w : r) {
-    seed = seed * 6364136223846793005ull + 1442695040888963407ull;
-    w = (uint32_t)(seed >> 32);
-  }
-  r = bn::low_bits(r, bits);
-  r.resize((bits + 31) / 32, 0);
-  r[(bits - 1) / 32] |= 1u << ((bits - 1) % 32);
-  r[0] |= 1u;
-  return r;
-}
-
-bn::Limbs pow2m1(size_t k) { return bn::sub(bn::pow2(k), bn::Limbs{1}); }
 
 // the committed 1024-bit RSA key (tests/golden/keys.json, rsa1024_committed)
 const bn::Limbs kP = from_hex(
@@ -66,61 +33,16 @@ const bn::Limbs kD = from_hex(
     "4e918092ff9188b23e2dbdc53a2bde555513af0ce651c30a7cbc1085669d468e776da240516cedc0ee3e6016018e65c396c38accbbe8c95af2"
     "6079fc048345d51a8174c2f22c29");
 
-// ---- the kernels' arithmetic, restated -------------------------------------------------------------------
-struct Sim {
-  int S1, W;
+// ---- the kernels' order of products over Mont1Sim ----------------------------------------------------------
+struct Sim : Mont1Sim {
   bool qp;
-  uint32_t mask, n0;
   std::vector<uint32_t> c1;  // ladder1_consts
-  std::string id;
   const uint32_t* vec(int slot) const { return c1.data() + (size_t)slot * S1; }
-
-  uint64_t add64(uint64_t a, uint64_t b) const {
-    if (a + b < a) die(id + ": a lazy sum passed 2^64");
-    return a + b;
-  }
-  uint64_t mad(uint32_t a, uint32_t b, uint64_t c) const { return add64((uint64_t)a * b, c); }
-
-  // Mont1<S1, W, QP>::step
-  void step(std::vector<uint64_t>& t, const std::vector<uint32_t>& a, const uint32_t* n, uint32_t b, bool QP) const {
-    t[0] = mad(a[0], b, t[0]);
-    const uint32_t m = (QP ? (uint32_t)t[0] : (uint32_t)t[0] * n0) & mask;
-    for (int l = 1; l < S1; ++l) t[l] = mad(a[l], b, t[l]);
-    const uint64_t u0 = mad(m, n[0], t[0]);
-    if (u0 & mask) die(id + ": the quotient digit does not clear limb 0");
-    t[0] = mad(m, n[1], add64(t[1], u0 >> W));
-    for (int l = 2; l < S1; ++l) t[l - 1] = mad(m, n[l], t[l]);
-    t[S1 - 1] = 0;
-  }
-  // Mont1::settle: fully normalised limbs, no carry out of the top limb
-  void settle(const std::vector<uint64_t>& t, std::vector<uint32_t>& a) const {
-    uint64_t c = 0;
-    for (int l = 0; l < S1; ++l) {
-      const uint64_t v = add64(t[l], c);
-      a[l] = (uint32_t)v & mask;
-      c = v >> W;
-    }
-    if (c) die(id + ": settle carries out of the top limb (value >= R1)");
-  }
-  // Lad1::mul: a <- MonPro(a, b), limb i of b = ld(i); the steps run in limb order whatever the blocking
-  template <class F>
-  void mul(std::vector<uint32_t>& a, const uint32_t* n, bool QP, F ld) const {
-    for (int l = 0; l < S1; ++l)
-      if (a[l] > mask) die(id + ": multiplicand limb not normalised");
-    std::vector<uint64_t> t(S1, 0);
-    for (int i = 0; i < S1; ++i) {
-      const uint32_t b = ld(i);
-      if (b > mask) die(id + ": multiplier limb not normalised");
-      step(t, a, n, b, QP);
-    }
-    settle(t, a);
-  }
-  bn::Limbs value(const std::vector<uint32_t>& a) const { return bn::from_rw(a.data(), S1, W); }
 };
 
 // x^E mod N as k_modexp1_pre + k_modexp1_ladder compute it; x < 2N in S1 limbs
 bn::Limbs replay(const Sim& s, const bn::Limbs& N, const bn::Limbs& x, const bn::Limbs& E) {
-  const uint32_t* n = s.vec(0 /* kL1Mod */);
+  const uint32_t* n = s.vec(kL1Mod);
   const bn::Limbs mod_val = bn::from_rw(n, s.S1, s.W), bound = bn::add(mod_val, mod_val);
   auto in_bound = [&](const std::vector<uint32_t>& a, const char* what) {
     if (bn::cmp(s.value(a), bound) >= 0) die(s.id + ": " + what + " not below twice the product modulus");
@@ -130,7 +52,7 @@ bn::Limbs replay(const Sim& s, const bn::Limbs& N, const bn::Limbs& x, const bn:
   // pre
   std::vector<std::vector<uint32_t>> tab(nodd);
   std::vector<uint32_t> a = bn::to_rw(x, s.S1, s.W);
-  const uint32_t* r2 = s.vec(3 /* kL1R2 */);
+  const uint32_t* r2 = s.vec(kL1R2);
   s.mul(a, n, s.qp, [&](int i) { return r2[i]; });
   in_bound(a, "x R1");
   tab[0] = a;
@@ -148,7 +70,7 @@ bn::Limbs replay(const Sim& s, const bn::Limbs& N, const bn::Limbs& x, const bn:
   }
   // ladder
   if (!sched.empty()) a = tab[sched[0]];
-  else a.assign(s.vec(2 /* kL1Rmod */), s.vec(2) + s.S1);
+  else a.assign(s.vec(kL1Rmod), s.vec(kL1Rmod) + s.S1);
   for (size_t k = 1; k < sched.size(); ++k) {
     const uint32_t e = sched[k];
     for (uint32_t q = e >> 16; q > 0; --q) {
@@ -162,17 +84,10 @@ bn::Limbs replay(const Sim& s, const bn::Limbs& N, const bn::Limbs& x, const bn:
       in_bound(a, "window product");
     }
   }
-  const uint32_t* nn = s.vec(1 /* kL1N */);
+  const uint32_t* nn = s.vec(kL1N);
   s.mul(a, nn, false, [](int i) { return i == 0 ? 1u : 0u; });
   if (bn::cmp(s.value(a), N) > 0) die(s.id + ": the product by 1 is above N");
-  int c = 0;
-  for (int l = 0; l < s.S1; ++l) c = a[l] > nn[l] ? 1 : (a[l] < nn[l] ? -1 : c);
-  uint32_t br = 0;
-  for (int l = 0; l < s.S1; ++l) {
-    const uint32_t d = a[l] - nn[l] - br;
-    br = d >> 31;
-    a[l] = c >= 0 ? (d & s.mask) : a[l];
-  }
+  s.canon(a, nn);
   for (int l = 0; l < s.S1; ++l)
     if (a[l] > s.mask) die(s.id + ": result limb not normalised");
   return s.value(a);
@@ -191,18 +106,18 @@ void check_ladder(const char* name, const bn::Limbs& N, int S1, bool qp, const s
   // the constants against bn::
   const bn::Limbs R1 = bn::pow2((size_t)W * S1);
   if (((uint64_t)s.n0 * N[0] + 1) & s.mask) die(s.id + ": n0 is not -N^-1 mod 2^W");
-  const bn::Limbs mod_val = bn::from_rw(s.vec(0), S1, W);
+  const bn::Limbs mod_val = bn::from_rw(s.vec(kL1Mod), S1, W);
   if (qp) {
     if (bn::cmp(mod_val, bn::mul(N, bn::Limbs{s.n0})) != 0) die(s.id + ": kL1Mod is not N n0");
-    if ((s.vec(0)[0] & s.mask) != s.mask) die(s.id + ": N~ is not -1 mod 2^W");
+    if ((s.vec(kL1Mod)[0] & s.mask) != s.mask) die(s.id + ": N~ is not -1 mod 2^W");
     if (bn::cmp(bn::mul(mod_val, bn::Limbs{4}), R1) > 0) die(s.id + ": 4 N~ > R1");
   } else {
     if (bn::cmp(mod_val, N) != 0) die(s.id + ": kL1Mod is not N");
     if (bn::cmp(bn::mul(N, bn::Limbs{4}), R1) > 0) die(s.id + ": 4 N > R1");
   }
-  if (bn::cmp(bn::from_rw(s.vec(1), S1, W), N) != 0) die(s.id + ": kL1N is not N");
-  if (bn::cmp(bn::from_rw(s.vec(2), S1, W), bn::mod(R1, N)) != 0) die(s.id + ": kL1Rmod is not R1 mod N");
-  if (bn::cmp(bn::from_rw(s.vec(3), S1, W), bn::mod(bn::mul(R1, R1), N)) != 0) die(s.id + ": kL1R2 is not R1^2 mod N");
+  if (bn::cmp(bn::from_rw(s.vec(kL1N), S1, W), N) != 0) die(s.id + ": kL1N is not N");
+  if (bn::cmp(bn::from_rw(s.vec(kL1Rmod), S1, W), bn::mod(R1, N)) != 0) die(s.id + ": kL1Rmod is not R1 mod N");
+  if (bn::cmp(bn::from_rw(s.vec(kL1R2), S1, W), bn::mod(bn::mul(R1, R1), N)) != 0) die(s.id + ": kL1R2 is not R1^2 mod N");
   const bn::Limbs one{1}, N2 = bn::add(N, N);
   std::vector<bn::Limbs> xs = {{}, one, bn::sub(N, one), N, bn::sub(N2, one),
                                bn::mod(lcg_odd(bn::bit_length(N) + 7, 11), N2)};

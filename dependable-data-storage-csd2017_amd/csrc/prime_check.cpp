@@ -1,44 +1,25 @@
 // CPU check of the strong probable-prime kernel (ddshe_prime.hpp) and of the host arithmetic of the prime search
 // and the key generators (ddshe_prime_plan.hpp). No HIP. k_strong1's arithmetic is restated limb by limb: n0 by
 // Newton, R1 mod N by doubling from the power of two below N, b R1 mod N by doubling, Mont1::step and settle
-// (ddshe_fold.hpp) with every lazy 64-bit sum checked against 2^64, the doubling path of base 2, the canonical
+// with every lazy 64-bit sum checked against 2^64 (check_mont1.hpp), the doubling path of base 2, the canonical
 // subtraction after every product and the +-1 bookkeeping over the bits of N - 1, and compared with a strong test
 // written with bn::powmod. k_prime_sieve's residues and first offsets, the draws and tags, the classes and the
 // Paillier finishing step are checked against bn:: arithmetic. Exits non-zero on the first failed check, naming
-// it; prints "ok <case>" lines and "prime_check: all passed" (tests/test_prime_check.py).
+// it; prints "ok <case>" lines and "prime_check: all passed" (tests/test_cpu_checks.py).
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "bn_host.hpp"
+#include "check_mont1.hpp"
+#include "check_util.hpp"
 #include "ddshe_prime_plan.hpp"
 
 using namespace ddshe;
+using namespace ddshe::check;
 
 namespace {
 
-[[noreturn]] void die(const std::string& what) {
-  std::printf("FAIL: %s\n", what.c_str());
-  std::fflush(stdout);
-  std::exit(1);
-}
-
-// an odd value of exactly `bits` bits from a fixed 64-bit LCG (Knuth's MMIX constants)
-bn::Limbs lcg_odd(size_t bits, uint64_t seed) {
-  bn::Limbs r((bits + 31) / 32);
-  for (auto& w : r) {
-    seed = seed * 6364136223846793005ull + 1442695040888963407ull;
-    w = (uint32_t)(seed >> 32);
-  }
-  r = bn::low_bits(r, bits);
-  r.resize((bits + 31) / 32, 0);
-  r[(bits - 1) / 32] |= 1u << ((bits - 1) % 32);
-  r[0] |= 1u;
-  return r;
-}
-
-bn::Limbs pow2m1(size_t k) { return bn::sub(bn::pow2(k), bn::Limbs{1}); }
 bn::Limbs proth(uint32_t k, size_t e) { return bn::add(bn::mul(bn::Limbs{k}, bn::pow2(e)), bn::Limbs{1}); }
 
 // the strong test as the definition states it, in bn:: arithmetic
@@ -58,59 +39,14 @@ bool strong_ref(const bn::Limbs& N, const bn::Limbs& b) {
 }
 
 // ---- the kernel's arithmetic, restated --------------------------------------------------------------------
-struct Sim {
-  int S1, W;
-  uint32_t mask, n0;
+// Mont1Sim with the plain quotient against the lane's own N, and what Str1 adds to it
+struct Sim : Mont1Sim {
   std::vector<uint32_t> n;
-  std::string id;
 
-  uint64_t add64(uint64_t a, uint64_t b) const {
-    if (a + b < a) die(id + ": a lazy sum passed 2^64");
-    return a + b;
-  }
-  uint64_t mad(uint32_t a, uint32_t b, uint64_t c) const { return add64((uint64_t)a * b, c); }
-  // Mont1<S1, W, false>::step
-  void step(std::vector<uint64_t>& t, const std::vector<uint32_t>& a, uint32_t b) const {
-    t[0] = mad(a[0], b, t[0]);
-    const uint32_t m = ((uint32_t)t[0] * n0) & mask;
-    for (int l = 1; l < S1; ++l) t[l] = mad(a[l], b, t[l]);
-    const uint64_t u0 = mad(m, n[0], t[0]);
-    if (u0 & mask) die(id + ": the quotient digit does not clear limb 0");
-    t[0] = mad(m, n[1], add64(t[1], u0 >> W));
-    for (int l = 2; l < S1; ++l) t[l - 1] = mad(m, n[l], t[l]);
-    t[S1 - 1] = 0;
-  }
-  void settle(const std::vector<uint64_t>& t, std::vector<uint32_t>& a) const {
-    uint64_t c = 0;
-    for (int l = 0; l < S1; ++l) {
-      const uint64_t v = add64(t[l], c);
-      a[l] = (uint32_t)v & mask;
-      c = v >> W;
-    }
-    if (c) die(id + ": settle carries out of the top limb (value >= R1)");
-  }
-  // Lad1::mul: a <- MonPro(a, b)
   void mul(std::vector<uint32_t>& a, const std::vector<uint32_t>& b) const {
-    std::vector<uint64_t> t(S1, 0);
-    for (int i = 0; i < S1; ++i) {
-      if (b[i] > mask || a[i] > mask) die(id + ": operand limb not normalised");
-      step(t, a, b[i]);
-    }
-    settle(t, a);
+    Mont1Sim::mul(a, n.data(), false, [&](int i) { return b[i]; });
   }
-  // Str1::canon: a < 2N -> canonical
-  void canon(std::vector<uint32_t>& a) const {
-    if (bn::cmp(bn::from_rw(a.data(), S1, W), bn::mul(bn::from_rw(n.data(), S1, W), bn::Limbs{2})) >= 0)
-      die(id + ": a value to be made canonical is not below 2N");
-    int c = 0;
-    for (int l = 0; l < S1; ++l) c = a[l] > n[l] ? 1 : (a[l] < n[l] ? -1 : c);
-    uint32_t br = 0;
-    for (int l = 0; l < S1; ++l) {
-      const uint32_t d = a[l] - n[l] - br;
-      br = d >> 31;
-      a[l] = c >= 0 ? (d & mask) : a[l];
-    }
-  }
+  void canon(std::vector<uint32_t>& a) const { Mont1Sim::canon(a, n.data()); }
   // Str1::shl
   void shl(std::vector<uint32_t>& a, uint32_t sh) const {
     uint32_t c = 0;

@@ -6,55 +6,24 @@
 // operand of a product, and b limbs at their maxima over more than kSumRows rows per pair. No HIP. Exits
 // non-zero on the first failed check, naming it.
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "bn_host.hpp"
+#include "check_util.hpp"
+#include "ddshe_consts.hpp"
 
 using namespace ddshe;
+using namespace ddshe::check;
 typedef unsigned __int128 u128;
 
 namespace {
 
-constexpr int S = 76, H = S / 2, PF = 4, W = 28;
+constexpr int S = kFoldSqLimbs, H = S / 2, PF = 4, W = 28;
 constexpr uint32_t kMask = (1u << W) - 1u;
-constexpr int kSumRows = 8;  // MontUnit::kSumRows
+constexpr int kSumRows = kFoldUnitSumRows;
 
-[[noreturn]] void die(const std::string& what) {
-  std::printf("FAIL: %s\n", what.c_str());
-  std::fflush(stdout);
-  std::exit(1);
-}
-void need(bool ok, const std::string& what) {
-  if (!ok) die(what);
-}
-
-bn::Limbs from_hex(const char* s) {
-  bn::Limbs r;
-  size_t n = 0;
-  while (s[n]) ++n;
-  for (size_t i = 0; i < n; ++i) {
-    const char c = s[n - 1 - i];
-    const uint32_t d = c <= '9' ? c - '0' : (c | 0x20) - 'a' + 10;
-    if (i / 8 >= r.size()) r.push_back(0);
-    r[i / 8] |= d << (4 * (i % 8));
-  }
-  bn::trim(r);
-  return r;
-}
-
-uint64_t g_lcg = 0x243F6A8885A308D3ull;
-uint32_t rnd32() {
-  g_lcg = g_lcg * 6364136223846793005ull + 1442695040888963407ull;
-  return (uint32_t)(g_lcg >> 32);
-}
-bn::Limbs rnd_below(const bn::Limbs& m) {
-  bn::Limbs r(m.size() + 1);
-  for (auto& w : r) w = rnd32();
-  bn::trim(r);
-  return bn::mod(r, m);
-}
+Lcg g_rng{0x243F6A8885A308D3ull};
 
 typedef std::vector<uint32_t> Vec;  // S limbs of W bits
 Vec load(const bn::Limbs& v) {
@@ -218,8 +187,8 @@ void check_modulus(const char* name, const bn::Limbs& n) {
   const size_t count = 29, G = 3;
   std::vector<Vec> w, b;
   for (size_t j = 0; j < count; ++j) {
-    w.push_back(load(j == 4 ? one : j == 7 || j == 11 ? bn::sub(nq2, one) : rnd_below(nq2)));
-    b.push_back(load(j == 5 ? bn::Limbs{} : j == 0 || j == 8 || j == 11 ? bn::sub(n2, one) : rnd_below(n2)));
+    w.push_back(load(j == 4 ? one : j == 7 || j == 11 ? bn::sub(nq2, one) : g_rng.rnd_below(nq2)));
+    b.push_back(load(j == 5 ? bn::Limbs{} : j == 0 || j == 8 || j == 11 ? bn::sub(n2, one) : g_rng.rnd_below(n2)));
   }
   for (size_t g = 0; g < G; ++g) {
     const Out o = fold_pair(cx, w, b, g, G);
@@ -277,17 +246,9 @@ void check_extremes() {
 }  // namespace
 
 int main() {
-  // the committed 2048-bit Paillier key's n (tests/golden/keys.json, paillier2048_committed)
-  const bn::Limbs n_committed = from_hex(
-      "9bb877201eaff7b911662e986eef4a33cb9a83535b5a85820a8b9969ecffa2ab49fbb4d5cce1ab05d6804929e2eeaf76"
-      "9c0d35ca78e57d1a98201fea9f98350b9e8f3ecd11da17c0b61a2a3f4c1fecd9836d148e5f7c1cca48012d7c80b9871b"
-      "1087dfa59354897bd5cf7209c7d30830fb7dc284b6f62fe2293e5f1dce0b716940bce5afa3e1433ddfe979cac6a12bac"
-      "a546e946ecef03f111d4f678f592c4321ea53926c4ed7bbd13e10acae611f4fd7a87ba0f0a81b15611a477b158962955"
-      "e2f8253df997989345a4d7ef946937e8f028b26d0a2a7de1022a23ad43efbfa90dc83d66158a21a66c3cbe9d7df5452d"
-      "0dbbe090f90c2072a8adf6fbc7184213");
   const bn::Limbs one{1};
   check_extremes();
-  check_modulus("committed n", n_committed);
+  check_modulus("committed n", kCommittedN);
   bn::Limbs n_min = bn::add(bn::isqrt(bn::pow2(3134)), one);
   if ((n_min[0] & 1u) == 0) n_min = bn::add(n_min, one);
   check_modulus("smallest n of the shape", n_min);

@@ -1,145 +1,31 @@
 // CPU check of the unit form of the digit mirror (ddshe_foldunit.hpp): bn::inv_mod and bn::inv_finish
-// against bn:: arithmetic, then a limb-by-limb replay, on four emulated lanes of 19 limbs with every lazy
-// sum checked against 2^64 (and every 32-bit sum against 2^32), of the up and down passes of the batch
+// against bn:: arithmetic, then a limb-by-limb replay, on four emulated lanes of 19 limbs (check_digits.hpp) with
+// every lazy sum checked against 2^64 (and every 32-bit sum against 2^32), of the up and down passes of the batch
 // inversion (k_inv_up, k_inv_down, two levels and the host finish), of the unit fold step with its running
 // sum S (MontUnit::step, carry), and of the join (k_unit_join). No HIP. Exits non-zero on the first failed
 // check, naming it.
 #include <cstdio>
-#include <cstdlib>
 #include <string>
 #include <vector>
 
 #include "bn_host.hpp"
+#include "check_digits.hpp"
+#include "check_util.hpp"
+#include "ddshe_consts.hpp"
 
 using namespace ddshe;
-typedef unsigned __int128 u128;
+using namespace ddshe::check;
 
 namespace {
 
-constexpr int S = 76, TPI = 4, L = S / TPI, W = 28, SW = 148;
-constexpr uint32_t kMask = (1u << W) - 1u;
-constexpr int kSumRows = 8;                      // MontUnit::kSumRows
-constexpr uint64_t kMaxRowsPerGroup = 1ull << 26;  // kFoldUnitMaxRowsPerGroup
+constexpr int kSumRows = kFoldUnitSumRows;
 
-[[noreturn]] void die(const std::string& what) {
-  std::printf("FAIL: %s\n", what.c_str());
-  std::fflush(stdout);
-  std::exit(1);
-}
-void need(bool ok, const std::string& what) {
-  if (!ok) die(what);
-}
+Lcg g_rng{0x13198A2E03707344ull};
 
-bn::Limbs from_hex(const char* s) {
-  bn::Limbs r;
-  size_t n = 0;
-  while (s[n]) ++n;
-  for (size_t i = 0; i < n; ++i) {
-    const char c = s[n - 1 - i];
-    const uint32_t d = c <= '9' ? c - '0' : (c | 0x20) - 'a' + 10;
-    if (i / 8 >= r.size()) r.push_back(0);
-    r[i / 8] |= d << (4 * (i % 8));
-  }
-  bn::trim(r);
-  return r;
-}
-
-uint64_t g_lcg = 0x13198A2E03707344ull;
-uint32_t rnd32() {
-  g_lcg = g_lcg * 6364136223846793005ull + 1442695040888963407ull;
-  return (uint32_t)(g_lcg >> 32);
-}
-bn::Limbs rnd_below(const bn::Limbs& m) {
-  bn::Limbs r(m.size() + 1);
-  for (auto& w : r) w = rnd32();
-  bn::trim(r);
-  return bn::mod(r, m);
-}
-
-struct Lanes {
-  u128 t[TPI][L];
-  void add(int r, int l, u128 v) {
-    t[r][l] += v;
-    need(t[r][l] >> 64 == 0, "a lazy sum passed 2^64");
-  }
-};
-struct Dig {
-  uint32_t a[TPI][L];
-};
-
-Dig load(const bn::Limbs& v) {
-  need(bn::bit_length(v) <= (size_t)W * S, "load: value >= R");
-  const std::vector<uint32_t> x = bn::to_rw(v, S, W);
-  Dig d;
-  for (int r = 0; r < TPI; ++r)
-    for (int l = 0; l < L; ++l) d.a[r][l] = x[r * L + l];
-  return d;
-}
-bn::Limbs value(const Dig& d) { return bn::from_rw(&d.a[0][0], S, W); }
-bool normalised(const Dig& d) {
-  for (int r = 0; r < TPI; ++r)
-    for (int l = 0; l < L; ++l)
-      if (d.a[r][l] > kMask) return false;
-  return true;
-}
-
-// pass 2 of a CIOS step on every lane (Mont::step, MontSq::reduce): t = (t + m·mod) / 2^W
-void reduce(Lanes& t, const Dig& md, uint32_t m) {
-  uint32_t lo0[TPI];
-  for (int r = 0; r < TPI; ++r) {
-    u128 u0 = t.t[r][0] + (u128)m * md.a[r][0];
-    need(u0 >> 64 == 0, "u0 passed 2^64");
-    lo0[r] = (uint32_t)u0 & kMask;
-    const u128 t1 = t.t[r][1];
-    t.t[r][0] = 0;
-    t.add(r, 0, t1 + (u0 >> W) + (u128)m * md.a[r][1]);
-    for (int l = 2; l < L; ++l) {
-      const u128 tl = t.t[r][l];
-      t.t[r][l - 1] = 0;
-      t.add(r, l - 1, tl + (u128)m * md.a[r][l]);
-    }
-  }
-  need(lo0[0] == 0, "the quotient digit does not clear limb 0");
-  for (int r = 0; r < TPI; ++r) t.t[r][L - 1] = lo0[(r + 1) % TPI];
-}
-
-// Mont::settle: lazy sums -> almost-normalised limbs; the top lane's carry is dropped (must be 0)
-void settle(const Lanes& t, Dig& a) {
-  u128 cout[TPI];
-  for (int r = 0; r < TPI; ++r) {
-    u128 c = 0;
-    for (int l = 0; l < L; ++l) {
-      const u128 v = t.t[r][l] + c;
-      need(v >> 64 == 0, "settle: v passed 2^64");
-      a.a[r][l] = (uint32_t)v & kMask;
-      c = v >> W;
-    }
-    cout[r] = c;
-  }
-  need(cout[TPI - 1] == 0, "settle: carry out of the top lane");
-  for (int r = 1; r < TPI; ++r) {
-    a.a[r][0] += (uint32_t)cout[r - 1] & kMask;
-    a.a[r][1] += (uint32_t)(cout[r - 1] >> W);
-  }
-}
-
-// Mont::normalize, value-preserving: a flat carry pass (limbs may be anything below 2^32 - 2^(32-W))
-void normalize(Dig& a) {
-  uint32_t c = 0;
-  for (int r = 0; r < TPI; ++r)
-    for (int l = 0; l < L; ++l) {
-      const uint64_t v = (uint64_t)a.a[r][l] + c;
-      need(v >> 32 == 0, "normalize: a 32-bit sum wrapped");
-      a.a[r][l] = (uint32_t)v & kMask;
-      c = (uint32_t)(v >> W);
-    }
-  need(c == 0, "normalize: carry out");
-}
-
-struct Ctx {
-  bn::SqDigits sd;
-  bn::Limbs N, R;
-  Dig n, nq, C, Rmod, R2;
+// the digit context of check_digits.hpp with what the inversion and the join need on the lanes
+struct Ctx : DigCtx {
+  bn::Limbs R;
+  Dig n, Rmod, R2;
 };
 
 // Mont<S, TPI, W>::mul_col with the modulus n and k = -n⁻¹ mod 2^W: a <- a·B·R⁻¹, B fully normalised
@@ -157,29 +43,6 @@ void mont_mul(const Ctx& cx, Dig& a, const Dig& B) {
     reduce(t, cx.n, m);
   }
   settle(t, a);
-}
-
-// k_to_digits, as in sq_check: row X (SW limbs) -> (w, c), fully normalised
-void to_digits(const Ctx& cx, const bn::Limbs& X, Dig& w, Dig& c) {
-  const std::vector<uint32_t> x = bn::to_rw(X, SW, W);
-  Lanes tA{}, tB{};
-  for (int r = 0; r < TPI; ++r)
-    for (int l = 0; l < L; ++l) {
-      tA.t[r][l] = x[r * L + l];
-      tB.t[r][l] = cx.C.a[r][l];
-    }
-  for (int i = 0; i < S; ++i) {
-    const uint32_t qa = (uint32_t)tA.t[0][0] & kMask;
-    tB.add(0, 0, (u128)cx.sd.k * (kMask - qa));
-    const uint32_t mB = (uint32_t)tB.t[0][0] & kMask;
-    reduce(tA, cx.nq, qa);
-    reduce(tB, cx.nq, mB);
-  }
-  for (int j = 0; S + j < SW; ++j) tA.add(j / L, j % L, x[S + j]);
-  settle(tA, w);
-  settle(tB, c);
-  normalize(w);
-  normalize(c);
 }
 
 // MontUnit::mul_row_chain: (x0, x1) <- (x0, x1)·w·R⁻¹, almost normalised
@@ -293,13 +156,10 @@ std::vector<Dig> inv_down(const Ctx& cx, const std::vector<Dig>& w, const Level&
 
 Ctx make_ctx(const bn::Limbs& n, const std::string& tag) {
   Ctx cx;
-  cx.N = bn::mul(n, n);
-  need(bn::sq_consts(cx.N, S, W, &cx.sd), tag + "n^2 not accepted");
+  cx.init(n, tag);
   cx.R = bn::pow2((size_t)W * S);
   need(bn::cmp(cx.sd.R2, bn::mod(bn::mul(cx.R, cx.R), n)) == 0, tag + "R^2 mod n");
   cx.n = load(cx.sd.n);
-  cx.nq = load(cx.sd.nq);
-  cx.C = load(cx.sd.C);
   cx.Rmod = load(cx.sd.Rmod);
   cx.R2 = load(cx.sd.R2);
   return cx;
@@ -347,7 +207,7 @@ void check_modulus(const char* name, const bn::Limbs& n) {
   std::vector<Dig> w, c;
   for (size_t j = 0; w.size() < 37; ++j) {
     Dig wd, cd;
-    to_digits(cx, j < rows.size() ? rows[j] : rnd_below(cx.N), wd, cd);
+    to_digits(cx, j < rows.size() ? rows[j] : g_rng.rnd_below(cx.N), wd, cd);
     bn::Limbs unused;
     if (!bn::inv_mod(value(wd), n, &unused)) {
       std::vector<Dig> w1(11, wd), c1(11, cd);
@@ -413,7 +273,7 @@ void check_modulus(const char* name, const bn::Limbs& n) {
   // limbs of S between two carry passes: all ones after a pass (plus the lane carry), then kSumRows rows of
   // all-ones b limbs
   {
-    const bn::Limbs smax = bn::mul(bn::from_u64(kMaxRowsPerGroup), bn::sub(n2, one));
+    const bn::Limbs smax = bn::mul(bn::from_u64(kFoldUnitMaxRowsPerGroup), bn::sub(n2, one));
     need(bn::cmp(smax, cx.R) < 0, tag + "S of the largest group >= R");
     Dig s = load(bn::sub(cx.R, one)), ones = s;
     for (int r = 1; r < TPI; ++r) s.a[r][0] += (1u << (32 - W)) - 1u;
@@ -440,11 +300,11 @@ void check_inv_mod(const bn::Limbs& p, const bn::Limbs& q) {
   const bn::Limbs n = bn::mul(p, q), one{1};
   bn::Limbs x;
   for (int i = 0; i < 50; ++i) {
-    const bn::Limbs a = i == 0 ? one : i == 1 ? bn::sub(n, one) : rnd_below(n);
+    const bn::Limbs a = i == 0 ? one : i == 1 ? bn::sub(n, one) : g_rng.rnd_below(n);
     need(bn::inv_mod(a, n, &x), "inv_mod: a unit was refused");
     need(bn::cmp(x, n) < 0 && bn::cmp(bn::mulmod(a, x, n), one) == 0, "inv_mod: a·x != 1");
     // a >= m: reduced first
-    const bn::Limbs big = bn::add(a, bn::mul(n, bn::Limbs{rnd32() | 1u, rnd32()}));
+    const bn::Limbs big = bn::add(a, bn::mul(n, bn::Limbs{g_rng.rnd32() | 1u, g_rng.rnd32()}));
     bn::Limbs y;
     need(bn::inv_mod(big, n, &y) && bn::cmp(x, y) == 0, "inv_mod: a >= m");
   }
@@ -452,8 +312,8 @@ void check_inv_mod(const bn::Limbs& p, const bn::Limbs& q) {
   need(!bn::inv_mod(n, n, &x), "inv_mod: m accepted");
   need(!bn::inv_mod(bn::mul(n, bn::Limbs{3}), n, &x), "inv_mod: 3m accepted");
   for (int i = 0; i < 10; ++i) {
-    need(!bn::inv_mod(bn::mod(bn::mul(p, rnd_below(q)), n), n, &x), "inv_mod: a multiple of p accepted");
-    need(!bn::inv_mod(bn::add(bn::mul(q, bn::Limbs{rnd32() | 1u}), n), n, &x), "inv_mod: a multiple of q accepted");
+    need(!bn::inv_mod(bn::mod(bn::mul(p, g_rng.rnd_below(q)), n), n, &x), "inv_mod: a multiple of p accepted");
+    need(!bn::inv_mod(bn::add(bn::mul(q, bn::Limbs{g_rng.rnd32() | 1u}), n), n, &x), "inv_mod: a multiple of q accepted");
   }
   need(bn::inv_mod(bn::Limbs{3}, bn::Limbs{7}, &x) && bn::cmp(x, bn::Limbs{5}) == 0, "inv_mod: 3^-1 mod 7");
   need(!bn::inv_mod(bn::Limbs{5}, bn::Limbs{1}, &x), "inv_mod: modulus 1");
@@ -463,18 +323,10 @@ void check_inv_mod(const bn::Limbs& p, const bn::Limbs& q) {
 }  // namespace
 
 int main() {
-  // the committed 2048-bit Paillier key's n (tests/golden/keys.json, paillier2048_committed)
-  const bn::Limbs n_committed = from_hex(
-      "9bb877201eaff7b911662e986eef4a33cb9a83535b5a85820a8b9969ecffa2ab49fbb4d5cce1ab05d6804929e2eeaf76"
-      "9c0d35ca78e57d1a98201fea9f98350b9e8f3ecd11da17c0b61a2a3f4c1fecd9836d148e5f7c1cca48012d7c80b9871b"
-      "1087dfa59354897bd5cf7209c7d30830fb7dc284b6f62fe2293e5f1dce0b716940bce5afa3e1433ddfe979cac6a12bac"
-      "a546e946ecef03f111d4f678f592c4321ea53926c4ed7bbd13e10acae611f4fd7a87ba0f0a81b15611a477b158962955"
-      "e2f8253df997989345a4d7ef946937e8f028b26d0a2a7de1022a23ad43efbfa90dc83d66158a21a66c3cbe9d7df5452d"
-      "0dbbe090f90c2072a8adf6fbc7184213");
   const bn::Limbs one{1};
   // two primes whose product stands in for a key: 2^89 - 1 and 2^107 - 1
   check_inv_mod(bn::sub(bn::pow2(89), one), bn::sub(bn::pow2(107), one));
-  check_modulus("committed n", n_committed);
+  check_modulus("committed n", kCommittedN);
   bn::Limbs n_min = bn::add(bn::isqrt(bn::pow2(3134)), one);
   if ((n_min[0] & 1u) == 0) n_min = bn::add(n_min, one);
   need(bn::bit_length(bn::mul(n_min, n_min)) == 3135, "smallest n: bits(n^2)");

@@ -1,0 +1,71 @@
+"""The CPU check programs of csrc/ (built by build() into csrc/build/): each replays a kernel's arithmetic limb by
+limb, or the host arithmetic beside it, with every lazy sum checked against 2^64, and compares the result with
+bn:: integers; what each covers stands at the top of its csrc/<name>_check.cpp. A program prints "ok <case>" lines
+and closes with "<name>_check: all passed"; it exits non-zero, naming the check, on the first one that fails.
+
+A new check program adds one row to CHECKS. csrc/host_check and csrc/dec_check are run by
+tests/test_host_helpers.py and tests/test_read_dec_abi.py, which do more than this."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+BUILD = os.path.join(ROOT, "dependable-data-storage-csd2017_amd", "csrc", "build")
+
+_EXPROWS_SHAPES = [f"S = {s}" for s in (40, 76, 112, 148, 232)]
+
+# program -> the prefixes some output line must start with, and what else its output must satisfy
+CHECKS = {
+    # the base-n digit form mod n² (csrc/ddshe_foldsq.hpp), for the moduli tests/test_gpu_fold_sq.py folds
+    "sq_check": dict(
+        prefixes=["ok " + name for name in ("committed n", "2^2047 - 1", "smallest n of the shape",
+                                             "2^2071 - 1 (capacity)")],
+        extra=lambda lines: sum(ln.endswith("rejected") for ln in lines) >= 5),
+    # the unit form of the digit mirror (csrc/ddshe_foldunit.hpp): batch inversion, fold step, sum and join
+    "unit_check": dict(
+        prefixes=["ok " + name for name in ("inv_mod", "committed n", "smallest n of the shape",
+                                             "2^2071 - 1 (capacity)")]),
+    # the unit-form fold at one chain per lane (csrc/ddshe_foldunit1.hpp) and its all-ones extremes
+    "unit1_check": dict(
+        prefixes=["ok " + name for name in ("extremes", "committed n", "smallest n of the shape",
+                                             "2^2071 - 1 (capacity)")]),
+    # the one-bignum-per-lane modexp ladder (csrc/ddshe_ladder1.hpp) and RSA-CRT's host arithmetic
+    "ladder1_check": dict(
+        prefixes=[f"ok {case} S1 = {s1} {form} " for s1 in (20, 40) for form in ("QP", "plain")
+                  for case in ("all-ones at capacity", "seeded at capacity", "modulus 3")]
+        + [f"ok committed p S1 = {s1} QP" for s1 in (20, 40)]
+        + ["ok " + name for name in ("exponent rule", "crt constants", "plan committed key", "plan 531-bit factors",
+                                     "plan 545-bit factors", "plan 1091-bit factors", "plan 1118-bit factors",
+                                     "plan 1536 + 512-bit factors")]),
+    # the strong probable-prime kernel (csrc/ddshe_prime.hpp) and the key generators' host arithmetic
+    "prime_check": dict(
+        prefixes=[f"ok {case} S1 = {s1} " for s1 in (20, 40, 56)
+                  for case in ("modulus 3", "all-ones at capacity", "seeded at capacity", "pseudoprime 2047",
+                               "prime 65537")]
+        + ["ok " + case for case in ("Proth prime 3 2^534 + 1 S1 = 20", "Proth prime 93 2^1110 + 1 S1 = 40",
+                                     "Proth prime 145 2^1552 + 1 S1 = 56", "classes and default window",
+                                     "sieve table and residues", "draws and tags", "finishing steps")]),
+    # the per-row exponent ladder's and the weighted fold's host arithmetic (csrc/ddshe_exprows_plan.hpp,
+    # csrc/ddshe_wfold_plan.hpp)
+    "exprows_check": dict(
+        prefixes=[f"ok digit walk {case} " for case in ["modulus 3", "modulus of 33 bits", "modulus of 64 bits"]
+                  + _EXPROWS_SHAPES]
+        + [f"ok weighted combine {case} " for case in ["modulus of 33 bits", "modulus of 61 bits"] + _EXPROWS_SHAPES]
+        + ["ok " + case for case in ("window plans", "table columns and the 2^32 bound", "bucket digits",
+                                     "weighted edges (Q no unit")],
+        extra=lambda lines: not any(ln.startswith("FAIL") for ln in lines)),
+}
+
+
+@pytest.mark.parametrize("name", sorted(CHECKS))
+def test_check_program_passes(name):
+    exe = os.path.join(BUILD, name)
+    assert os.path.exists(exe), f"csrc/build/{name} is missing: build() makes it"
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
+    lines = run.stdout.splitlines()
+    assert lines[-1] == f"{name}: all passed"
+    for prefix in CHECKS[name]["prefixes"]:
+        assert any(ln.startswith(prefix) for ln in lines), prefix
+    assert CHECKS[name].get("extra", lambda lines: True)(lines)

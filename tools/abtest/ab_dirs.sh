@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build tools/abtest/ab_fold from up to four header directories (A/B tool, not product):
-#   ./ab_dirs.sh <dir0> <dir1> [dir2] [dir3]   (each holding ddshe_device.hpp / ddshe_fold.hpp / ddshe_launch.hpp)
+#   ./ab_dirs.sh <dir0> <dir1> [dir2] [dir3]   (each holding ddshe_device.hpp / ddshe_fold.hpp / ddshe_launch.hpp / ddshe_consts.hpp)
 # then on the GPU box: AB_NAME0=.. AB_NAME1=.. ./tools/abtest/ab_fold 10000000 9
 set -e
 cd "$(dirname "$0")"

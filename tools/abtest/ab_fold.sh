@@ -13,6 +13,8 @@ mkdir -p old abobj
 for f in ddshe_device.hpp ddshe_fold.hpp ddshe_launch.hpp; do
   git show "$OLD:dependable-data-storage-csd2017_amd/csrc/$f" > old/$f
 done
+# (the constants header exists from the commit that split it out of ddshe_launch.hpp)
+git show "$OLD:dependable-data-storage-csd2017_amd/csrc/ddshe_consts.hpp" > old/ddshe_consts.hpp 2>/dev/null || rm -f old/ddshe_consts.hpp
 V2=${AB_V2:--I$CSRC}
 V3=${AB_V3:--Iold}
 $HIPCC $FL -Iold -DKNAME=k_ab0 -c ab_fold.hip -o abobj/ab0.o &

@@ -8,7 +8,7 @@ CSRC=../../dependable-data-storage-csd2017_amd/csrc
 HIPCC=/opt/rocm/bin/hipcc
 FL="--offload-arch=gfx950 -O3 -std=c++17"
 mkdir -p committed abobj1
-for f in ddshe_device.hpp ddshe_fold.hpp ddshe_launch.hpp; do
+for f in ddshe_device.hpp ddshe_fold.hpp ddshe_launch.hpp ddshe_consts.hpp; do
   git show "HEAD:dependable-data-storage-csd2017_amd/csrc/$f" > committed/$f
 done
 $HIPCC $FL -Icommitted -DKNAME=k_ab0 -c ab_fold1.hip -o abobj1/ab0.o &

@@ -100,6 +100,6 @@ fold = fold.replace("uint32_t pre[2][M::kPF];  // first limb blocks of the next 
 assert "pre[M::kDepth]" in fold
 open(os.path.join(out, "ddshe_device.hpp"), "w").write("#define AB_DEPTH %d\n" % D + dev)
 open(os.path.join(out, "ddshe_fold.hpp"), "w").write(fold)
-for f in ("ddshe_launch.hpp", "ddshe_shapes.hpp"):
+for f in ("ddshe_launch.hpp", "ddshe_consts.hpp", "ddshe_shapes.hpp"):
     open(os.path.join(out, f), "w").write(open(os.path.join(SRC, f)).read())
 print("wrote", out, "depth", D)

@@ -6,7 +6,7 @@ process's environment selects. Run it once per kernel, one process each, on the 
     DDSHE_FOLD_UNIT1_MIN=2 python3 tools/fold_unit1_sweep.py    # k_fold_unit1 from two rows on
     DDSHE_FOLD_UNIT1=0     python3 tools/fold_unit1_sweep.py    # k_fold_unit
 
-and set kFoldUnit1RowsPerPair (csrc/ddshe_launch.hpp) from the smallest count at which the pair kernel wins.
+and set kFoldUnit1RowsPerPair (csrc/ddshe_consts.hpp) from the smallest count at which the pair kernel wins.
 Prints one JSON line: {"path", "calls", "ms": {rows: median}, "sha": {rows: digest of the value}}."""
 import hashlib
 import json
