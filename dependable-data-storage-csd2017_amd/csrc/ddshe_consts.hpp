@@ -16,10 +16,12 @@ enum { kConstN = 0, kConstRmod = 1, kConstR2 = 2, kConstOne = 3, kConstN2x = 4, 
 constexpr int kFoldSqLimbs = 76, kFoldSqWide = 148;
 enum { kSqNq = 0, kSqN = 1, kSqC = 2, kSqRmod = 3, kSqR2 = 4, kSqCount = 5 };  // kSqR2: R² mod n
 
-// Unit form of the mirror (ddshe_foldunit.hpp).
+// Unit form of the mirror (ddshe_foldunit.hpp), and the batch inversion it shares with the row-wise inverses
+// (ddshe_inv_plan.hpp).
 // rows per group of one inversion level, and the row count at or below which the host finishes
 constexpr size_t kInvFan = 32;
-// rows whose prefix products one upgrade pass holds in scratch (kFoldSqLimbs limbs each)
+// rows whose prefix products one pass holds in scratch (kFoldSqLimbs limbs each for the mirror's upgrade, S limbs
+// for the row-wise calls, which take fewer where that plane would exceed 1 GiB: inv_chunk_rows)
 constexpr size_t kInvChunkRows = (size_t)1 << 20;
 // rows per group k_fold_unit admits: the sum of the b stays below R
 constexpr size_t kFoldUnitMaxRowsPerGroup = (size_t)1 << 26;

@@ -28,8 +28,8 @@ int fold_unit_after() {
 hipError_t launch_inv_up(const uint32_t* Wp, size_t wstride, size_t count, const uint32_t* sq, uint32_t k,
                          uint32_t* Pfx, size_t pstride, uint32_t* T, size_t tstride, size_t ngroups, hipStream_t st) {
   if (ngroups == 0 || ngroups > count || pstride < count || tstride < ngroups) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((k_inv_up<kS, kTPI, kW>), dim3(grid_for(ngroups * kTPI)), dim3(256), 0, st, Wp, wstride, count, sq,
-                     k, Pfx, pstride, T, tstride, ngroups);
+  hipLaunchKernelGGL((k_inv_up<kS, kTPI, kW>), dim3(grid_for(ngroups * kTPI)), dim3(256), 0, st, Wp, wstride, count,
+                     sq + kSqN * kS, sq + kSqRmod * kS, k, Pfx, pstride, T, tstride, ngroups);
   return hipGetLastError();
 }
 
@@ -39,7 +39,7 @@ hipError_t launch_inv_down(const uint32_t* Wp, size_t wstride, size_t count, con
   if (ngroups == 0 || ngroups > count || pstride < count || vstride < ngroups) return hipErrorInvalidValue;
   if (C ? cstride < count : (!Inv || istride < count)) return hipErrorInvalidValue;
   hipLaunchKernelGGL((k_inv_down<kS, kTPI, kW>), dim3(grid_for(ngroups * kTPI)), dim3(256), 0, st, Wp, wstride, count,
-                     sq, k, Pfx, pstride, V, vstride, C, cstride, Inv, istride, ngroups);
+                     sq + kSqN * kS, k, Pfx, pstride, V, vstride, C, cstride, Inv, istride, ngroups);
   return hipGetLastError();
 }
 

@@ -23,13 +23,18 @@ namespace ddshe {
 // M(a, b) < a·b/R + n. Every stored value of the two passes is < 2n: with R > 2^(W+2)·n an operand pair
 // below (2n, 2ñ) gives a·b/R < n.
 
-// Up pass. Group g takes rows g, g + G, ... of the digit plane Wp (values < 2ñ): p = R mod n, then for
-// each row Pfx[., row] = p (fully normalised) and p <- M(p, w_row); T[., g] = the last p. Literally
+// The two kernels are shared by the mirror's upgrade (the half shape (76, 4, 28) with n, R mod n and k of the sq
+// block) and by the row-wise inverses and quotients mod N (ddshe_inv.hip: every lane-group shape with N, R mod N
+// and n0 of the modulus' constant block). There only R > 4N holds: operands below 2N give
+// M(a, b) < 4N²/R + N < 2N, so every stored prefix, total and start value stays below 2N all the same.
+
+// Up pass. Group g takes rows g, g + G, ... of the plane Wp (fully normalised values): p = R mod n (rmod), then
+// for each row Pfx[., row] = p (fully normalised) and p <- M(p, w_row); T[., g] = the last p. Literally
 // p_j = R^(1-j)·∏_{i<=j} w_i.
 template <int S, int TPI, int W>
 __global__ void __launch_bounds__(256) k_inv_up(const uint32_t* __restrict__ Wp, size_t wstride, size_t count,
-                                               const uint32_t* __restrict__ sq, uint32_t k,
-                                               uint32_t* __restrict__ Pfx, size_t pstride,
+                                               const uint32_t* __restrict__ nvec, const uint32_t* __restrict__ rmod,
+                                               uint32_t k, uint32_t* __restrict__ Pfx, size_t pstride,
                                                uint32_t* __restrict__ T, size_t tstride, size_t ngroups) {
   using G = Grp<S, TPI, W>;
   using M = Mont<S, TPI, W>;
@@ -38,8 +43,8 @@ __global__ void __launch_bounds__(256) k_inv_up(const uint32_t* __restrict__ Wp,
   const size_t grp = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / TPI;
   if (grp >= ngroups) return;
   uint32_t n[L], p[L];
-  g.load_vec(n, sq + kSqN * S);
-  g.load_vec(p, sq + kSqRmod * S);
+  g.load_vec(n, nvec);
+  g.load_vec(p, rmod);
   for (size_t row = grp; row < count; row += ngroups) {
     g.store_col(p, Pfx, pstride, row);
     M::mul_col(p, n, Wp, wstride, (uint32_t)row, k, g.top, g.bottom);
@@ -51,12 +56,17 @@ __global__ void __launch_bounds__(256) k_inv_up(const uint32_t* __restrict__ Wp,
 // Down pass. v = V[., g] = R/T_g, then the group's rows backwards: inv = M(v, p_{j-1}) = R/w_j;
 // with a c plane b_j = M(inv, c_j) = c_j/w_j (the literal value, < 2n, fully normalised) replaces c_j,
 // without one inv goes to Inv (the start values of the level below); v <- M(v, w_j) = R/p_{j-1}.
-template <int S, int TPI, int W>
+// Rows (level 0 of the row-wise calls): the numerator is read from a matrix of its own, row j at column
+// j·nmul of Num (nmul = 1: a column's rows; nmul = 0 with nstride = 1: one vector for every row, the literal 1
+// for the plain inverse, M(R/w, 1) = w⁻¹), and the quotient goes to Inv as a canonical residue.
+template <int S, int TPI, int W, bool Rows = false>
 __global__ void __launch_bounds__(256) k_inv_down(const uint32_t* __restrict__ Wp, size_t wstride, size_t count,
-                                                 const uint32_t* __restrict__ sq, uint32_t k,
+                                                 const uint32_t* __restrict__ nvec, uint32_t k,
                                                  const uint32_t* __restrict__ Pfx, size_t pstride,
                                                  const uint32_t* __restrict__ V, size_t vstride, uint32_t* C,
-                                                 size_t cstride, uint32_t* Inv, size_t istride, size_t ngroups) {
+                                                 size_t cstride, uint32_t* Inv, size_t istride, size_t ngroups,
+                                                 const uint32_t* __restrict__ Num = nullptr, size_t nstride = 0,
+                                                 uint32_t nmul = 0) {
   using G = Grp<S, TPI, W>;
   using M = Mont<S, TPI, W>;
   constexpr int L = G::L;
@@ -64,14 +74,18 @@ __global__ void __launch_bounds__(256) k_inv_down(const uint32_t* __restrict__ W
   const size_t grp = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / TPI;
   if (grp >= ngroups || grp >= count) return;
   uint32_t n[L], v[L], inv[L];
-  g.load_vec(n, sq + kSqN * S);
+  g.load_vec(n, nvec);
   g.load_col(v, V, vstride, grp);
   size_t row = grp + (count - 1 - grp) / ngroups * ngroups;  // the group's last row
   for (;;) {
 #pragma unroll
     for (int l = 0; l < L; ++l) inv[l] = v[l];
     M::mul_col(inv, n, Pfx, pstride, (uint32_t)row, k, g.top, g.bottom);
-    if (C) {
+    if constexpr (Rows) {
+      M::mul_col(inv, n, Num, nstride, (uint32_t)row * nmul, k, g.top, g.bottom);
+      g.canon(inv, n);
+      g.store_col(inv, Inv, istride, row);
+    } else if (C) {
       M::mul_col(inv, n, C, cstride, (uint32_t)row, k, g.top, g.bottom);
       M::normalize(inv, g.bottom);
       g.store_col(inv, C, cstride, row);

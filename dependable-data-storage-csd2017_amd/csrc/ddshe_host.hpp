@@ -105,6 +105,8 @@ struct Worker {
   // weighted fold: weights (int64), the call's row ids, block histograms, bucket sizes, the bucket list (its own
   // id buffer: the fold it feeds uses `ids` for live ranges)
   DevBuf wf_w, wf_ids, wf_hist, wf_cnt, wf_list;
+  // batched inversion (inv_device): the prefix products of a chunk's rows, the upper levels' planes
+  DevBuf inv_pfx, inv_lv;
   DevBuf crt[7];  // CRT scratch of Paillier encryption and decryption (encrypt_crt_device, decrypt_crt_device)
   hipEvent_t ev[4] = {};
   // decimal codec: double-buffered pinned chunks (chars, offsets), their device copies,
@@ -625,6 +627,12 @@ int modexp_device(Worker* w, hipStream_t st, ModConsts& mc, const bn::Limbs& E, 
 // With the context's timing on, the kernels' device time goes to total_ms and the ladders' to fold_ms.
 int exprows_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* d_x, size_t xstride,
                    const uint64_t* d_exps, size_t max_bits, size_t count, uint32_t* d_out, size_t ostride);
+// out[i] = num[i] * x[i]^-1 mod N (d_num == nullptr: x[i]^-1), canonical, on the device by Montgomery's trick
+// (ddshe_linear.cpp, ddshe_inv_plan.hpp): x and num rows as above, out must not overlap them. A row that is no
+// unit mod N: DDS_E_RANGE with *bad_row (nullable) one such row's index; rows of `out` may then have been
+// written. Synchronises the stream. With the context's timing on, the kernels' device time goes to total_ms.
+int inv_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* d_x, size_t xstride,
+               const uint32_t* d_num, size_t nstride, size_t count, uint32_t* d_out, size_t ostride, size_t* bad_row);
 int product_tree(dds_ctx* ctx, const std::vector<uint32_t>& h, size_t count, size_t len, size_t cap16, bn::Limbs* out);
 int fold_even_modulus(dds_ctx* ctx, const bn::Limbs& M, const std::vector<bn::Limbs>& xs, const std::vector<bool>& negs,
                       bn::Limbs* out);

@@ -242,11 +242,12 @@ __global__ void __launch_bounds__(256, 2) k_reduce_rows(uint32_t* __restrict__ X
   g.store_col(a, X, stride, grp);
 }
 
-// out[i] = A[i]*B[i] mod N (canonical), rW columns in and out
+// out[i] = A[i]*B[i] mod N (canonical), rW columns in and out, each at a stride of its own
 template <int S, int TPI, int W>
-__global__ void __launch_bounds__(256, 2) k_pairs(const uint32_t* __restrict__ A, const uint32_t* __restrict__ B,
-                                               size_t stride, size_t count, const uint32_t* __restrict__ consts,
-                                               uint32_t n0, uint32_t* __restrict__ O) {
+__global__ void __launch_bounds__(256, 2) k_pairs(const uint32_t* __restrict__ A, size_t astride,
+                                               const uint32_t* __restrict__ B, size_t bstride, size_t count,
+                                               const uint32_t* __restrict__ consts, uint32_t n0,
+                                               uint32_t* __restrict__ O, size_t ostride) {
   using G = Grp<S, TPI, W>;
   using M = Mont<S, TPI, W>;
   constexpr int L = G::L;
@@ -255,11 +256,11 @@ __global__ void __launch_bounds__(256, 2) k_pairs(const uint32_t* __restrict__ A
   if (grp >= count) return;
   uint32_t n[L], a[L];
   g.load_vec(n, consts + kConstN * S);
-  g.load_col(a, A, stride, grp);
-  M::mul_col(a, n, B, stride, (uint32_t)grp, n0, g.top, g.bottom);       // a*b*R^-1
+  g.load_col(a, A, astride, grp);
+  M::mul_col(a, n, B, bstride, (uint32_t)grp, n0, g.top, g.bottom);      // a*b*R^-1
   M::mul_col(a, n, consts + kConstR2 * S, 1, 0, n0, g.top, g.bottom);   // a*b
   g.canon(a, n);
-  g.store_col(a, O, stride, grp);
+  g.store_col(a, O, ostride, grp);
 }
 
 // ------------------------------------------------------------------------------
@@ -1286,19 +1287,28 @@ hipError_t launch_fold_tail(int S, const uint32_t* X, size_t xstride, size_t cou
 
 int tail_tpi() { return 16; }
 
+hipError_t launch_pairs_cols(int S, const uint32_t* A, size_t astride, const uint32_t* B, size_t bstride, size_t count,
+                             const uint32_t* consts, uint32_t n0, uint32_t* O, size_t ostride, hipStream_t st) {
+  if (count == 0) return hipSuccess;
+  if (astride < count || bstride < count || ostride < count || bstride > max_stride(S)) return hipErrorInvalidValue;
+  DDSHE_SWITCH(S, hipLaunchKernelGGL((k_pairs<S, TPI, W>), dim3(grid_for(count * TPI)), dim3(256), 0, st, A, astride, B,
+                                     bstride, count, consts, n0, O, ostride));
+  return hipGetLastError();
+}
+
 hipError_t launch_pairs(int S, const uint32_t* A, const uint32_t* B, size_t stride, size_t count,
                         const uint32_t* consts, uint32_t n0, uint32_t* O, hipStream_t st) {
   if (count == 0) return hipSuccess;
-  DDSHE_SWITCH(S, hipLaunchKernelGGL((k_pairs<S, TPI, W>), dim3(grid_for(count * TPI)), dim3(256), 0, st, A, B, stride,
-                                     count, consts, n0, O));
+  DDSHE_SWITCH(S, hipLaunchKernelGGL((k_pairs<S, TPI, W>), dim3(grid_for(count * TPI)), dim3(256), 0, st, A, stride, B,
+                                     stride, count, consts, n0, O, stride));
   return hipGetLastError();
 }
 
 hipError_t launch_pairs_tail(int S, const uint32_t* A, const uint32_t* B, size_t stride, size_t count,
                              const uint32_t* consts, uint32_t n0, uint32_t* O, hipStream_t st) {
   if (count == 0) return hipSuccess;
-  DDSHE_TAIL_SWITCH(S, hipLaunchKernelGGL((k_pairs<S, TPI, W>), dim3(grid_for(count * TPI)), dim3(256), 0, st, A, B,
-                                          stride, count, consts, n0, O));
+  DDSHE_TAIL_SWITCH(S, hipLaunchKernelGGL((k_pairs<S, TPI, W>), dim3(grid_for(count * TPI)), dim3(256), 0, st, A,
+                                          stride, B, stride, count, consts, n0, O, stride));
   return hipGetLastError();
 }
 

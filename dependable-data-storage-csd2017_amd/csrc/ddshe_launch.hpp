@@ -73,6 +73,20 @@ hipError_t launch_inv_up(const uint32_t* Wp, size_t wstride, size_t count, const
 hipError_t launch_inv_down(const uint32_t* Wp, size_t wstride, size_t count, const uint32_t* sq, uint32_t k,
                            const uint32_t* Pfx, size_t pstride, const uint32_t* V, size_t vstride, uint32_t* C,
                            size_t cstride, uint32_t* Inv, size_t istride, size_t ngroups, hipStream_t st);
+// The same pair mod N at every lane-group shape (ddshe_inv.hip), with N, R mod N of the modulus' constant block
+// and n0. X: the level's rows (fully normalised, below 2N), limb-major at xstride. launch_inv_down_n writes R/x to
+// Inv (an upper level); launch_inv_down_rows (level 0) writes Num[row]·x_row⁻¹ mod N, or x_row⁻¹ when Num is
+// null, canonical, to O. Strides within max_stride(S), count <= 2^30.
+hipError_t launch_inv_up_n(int S, const uint32_t* X, size_t xstride, size_t count, const uint32_t* consts,
+                           uint32_t n0, uint32_t* Pfx, size_t pstride, uint32_t* T, size_t tstride, size_t ngroups,
+                           hipStream_t st);
+hipError_t launch_inv_down_n(int S, const uint32_t* X, size_t xstride, size_t count, const uint32_t* consts,
+                             uint32_t n0, const uint32_t* Pfx, size_t pstride, const uint32_t* V, size_t vstride,
+                             uint32_t* Inv, size_t istride, size_t ngroups, hipStream_t st);
+hipError_t launch_inv_down_rows(int S, const uint32_t* X, size_t xstride, size_t count, const uint32_t* consts,
+                                uint32_t n0, const uint32_t* Pfx, size_t pstride, const uint32_t* V, size_t vstride,
+                                const uint32_t* Num, size_t nstride, uint32_t* O, size_t ostride, size_t ngroups,
+                                hipStream_t st);
 // Level 1 over a unit-form mirror: Q gets 3·kFoldSqLimbs limb rows per group (x0, x1, S = Σ b)
 hipError_t launch_fold_unit(const uint32_t* D, size_t stride, size_t count, const uint32_t* sq, uint32_t k, uint32_t* Q,
                             size_t qstride, size_t ngroups, hipStream_t st);
@@ -124,6 +138,9 @@ hipError_t launch_pairs_sos(int S, const uint32_t* A, const uint32_t* B, size_t 
                             const uint32_t* R2, uint32_t* out, hipStream_t st);
 hipError_t launch_pairs(int S, const uint32_t* A, const uint32_t* B, size_t stride, size_t count,
                         const uint32_t* consts, uint32_t n0, uint32_t* O, hipStream_t st);
+// the same with a base and a stride of its own for each of A, B and O (rows of three columns)
+hipError_t launch_pairs_cols(int S, const uint32_t* A, size_t astride, const uint32_t* B, size_t bstride, size_t count,
+                             const uint32_t* consts, uint32_t n0, uint32_t* O, size_t ostride, hipStream_t st);
 // the same in a tail (latency) shape: S = tail limbs, consts of the tail shape (a few pairs per launch)
 hipError_t launch_pairs_tail(int S, const uint32_t* A, const uint32_t* B, size_t stride, size_t count,
                              const uint32_t* consts, uint32_t n0, uint32_t* O, hipStream_t st);

@@ -71,6 +71,7 @@ EXPORTS = [
     "dds_paillier_keygen_batch", "dds_rsa_keygen_batch", "dds_ctx_get_prime_timing",
     "dds_modexp_rows", "dds_col_append_pow", "dds_exprows_plan", "dds_col_fold_weighted",
     "dds_col_fold_weighted_dec", "dds_fold_weighted_plan",
+    "dds_modinv_rows", "dds_col_append_inv", "dds_col_append_quot", "dds_col_append_mul",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -179,6 +180,10 @@ _sig("dds_exprows_plan", C.c_int, _sz, C.POINTER(C.c_int), _u64p)
 _sig("dds_col_fold_weighted", C.c_int, C.c_void_p, _u64p, _sz, _sz, _i64p, _sz, _u8p, _sz, _szp)
 _sig("dds_col_fold_weighted_dec", C.c_int, C.c_void_p, _u64p, _sz, _sz, _i64p, _sz, C.c_char_p, _sz, _szp)
 _sig("dds_fold_weighted_plan", C.c_int, _sz, _sz, _sz, C.POINTER(C.c_int), _u64p, _u64p)
+_sig("dds_modinv_rows", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, _sz, _u8p, _szp)
+_sig("dds_col_append_inv", C.c_int, C.c_void_p, C.c_void_p, _sz, _sz, _szp)
+_sig("dds_col_append_quot", C.c_int, C.c_void_p, C.c_void_p, _sz, C.c_void_p, _sz, _sz, _szp)
+_sig("dds_col_append_mul", C.c_int, C.c_void_p, C.c_void_p, _sz, C.c_void_p, _sz, _sz)
 _sig("dds_pair_modmul_dec", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _sz, _szp)
 _sig("dds_pair_stats", C.c_int, C.c_void_p, _u64p, _u64p)
 _sig("dds_pair_timing", C.c_int, C.c_void_p, _u64p, _u64p, _u64p, _u64p)
@@ -224,8 +229,9 @@ _sig("dds_mcol_fold_dec", C.c_int, C.c_void_p, _u64p, _sz, C.c_char_p, _sz, _szp
 
 
 class DDSError(RuntimeError):
-    def __init__(self, status: int, where: str):
+    def __init__(self, status: int, where: str, row=None):
         self.status = status
+        self.row = row  # the row-wise inversions' non-unit row (dds_modinv_rows, append_inv, append_quot), else None
         detail = _lib.dds_last_error().decode(errors="replace")
         super().__init__(f"{where}: {_lib.dds_strerror(status).decode()} ({detail})")
 
@@ -245,6 +251,16 @@ def _check(rc: int, where: str):
         raise NotFound(rc, where)
     if rc != DDS_OK:
         raise DDSError(rc, where)
+
+
+_NO_ROW = C.c_size_t(-1).value
+
+
+def _check_row(rc: int, where: str, bad):
+    """_check for the calls that name a row: a DDS_E_RANGE that set *bad_row carries it as .row"""
+    if rc == DDS_E_RANGE and bad.value != _NO_ROW:
+        raise DDSError(rc, where, bad.value)
+    _check(rc, where)
 
 
 def int_to_be(x: int, width: int) -> bytes:
@@ -674,6 +690,19 @@ class Engine:
         raw = bytes(out)
         return [int.from_bytes(raw[i * mb:(i + 1) * mb], "big") for i in range(len(bases))]
 
+    def modinv_rows(self, modulus: int, rows) -> list[int]:
+        """dds_modinv_rows: out[i] = rows[i]^-1 mod modulus (Enc(-m) = c^-1 mod n^2 for a Paillier ciphertext), by
+        one batch inversion on the GPU. A row that is not coprime to the modulus: DDSError with .row naming one."""
+        rows = [int(x) for x in rows]
+        mb = nbytes(modulus)
+        width = max([mb] + [nbytes(x) for x in rows])
+        out = (C.c_uint8 * (mb * max(1, len(rows))))()
+        bad = C.c_size_t(_NO_ROW)
+        _check_row(_lib.dds_modinv_rows(self._h, int_to_be(modulus, mb), mb, ints_to_be(rows, width), width, len(rows),
+                                        out, C.byref(bad)), "dds_modinv_rows", bad)
+        raw = bytes(out)
+        return [int.from_bytes(raw[i * mb:(i + 1) * mb], "big") for i in range(len(rows))]
+
     @staticmethod
     def exprows_plan(bits: int) -> tuple:
         """dds_exprows_plan: (window, Montgomery products per row) of a per-row ladder call whose largest
@@ -875,6 +904,23 @@ class Column(_Mutable):
         if len(e) != count:
             raise ValueError("one exponent per row")
         _check(_lib.dds_col_append_pow(self._h, src._h, first, count, e.ctypes.data_as(_u64p)), "dds_col_append_pow")
+
+    def append_inv(self, src: "Column", first: int, count: int):
+        """dds_col_append_inv: append the inverses of rows [first, first+count) of src (Enc(-m_i) for a Paillier
+        column). A row that is not coprime to the modulus: DDSError with .row (relative to first), nothing appended."""
+        bad = C.c_size_t(_NO_ROW)
+        _check_row(_lib.dds_col_append_inv(self._h, src._h, first, count, C.byref(bad)), "dds_col_append_inv", bad)
+
+    def append_quot(self, num: "Column", num_first: int, den: "Column", den_first: int, count: int):
+        """dds_col_append_quot: append num[num_first+i] * den[den_first+i]^-1 (Enc(m_num - m_den) for Paillier
+        columns). A den row that is not coprime to the modulus: DDSError with .row, nothing appended."""
+        bad = C.c_size_t(_NO_ROW)
+        _check_row(_lib.dds_col_append_quot(self._h, num._h, num_first, den._h, den_first, count, C.byref(bad)),
+                   "dds_col_append_quot", bad)
+
+    def append_mul(self, a: "Column", a_first: int, b: "Column", b_first: int, count: int):
+        """dds_col_append_mul: append a[a_first+i] * b[b_first+i] (Enc(m_a + m_b) for Paillier columns)."""
+        _check(_lib.dds_col_append_mul(self._h, a._h, a_first, b._h, b_first, count), "dds_col_append_mul")
 
     def _weighted_args(self, weights, row_ids, first, count):
         if isinstance(weights, np.ndarray) and weights.dtype == np.int64:

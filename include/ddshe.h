@@ -600,6 +600,26 @@ int dds_col_fold_weighted_dec(dds_col*, const uint64_t* row_ids, size_t first, s
 /* The default window and the number of fold products + host products the plan predicts. No GPU work. */
 int dds_fold_weighted_plan(size_t rows, size_t max_bits, size_t window_in, int* window, uint64_t* row_products,
                            uint64_t* host_products);
+/* Row-wise inverses, differences and sums: Enc(-m) = c^-1, Enc(m1 - m2) = c1 * c2^-1, Enc(m1 + m2) = c1 * c2, all
+ * mod N, row by row. The inverses of a batch come from one inversion of its product (Montgomery's trick, about four
+ * products per row) in chunks of 2^20 rows. N even or < 3: DDS_E_ARG. A row that is not coprime to N (0
+ * included): DDS_E_RANGE, and *bad_row (nullable) receives the index, relative to the call, of a row that is not:
+ * one of them, not necessarily the one with the smallest index. On any error the output is unchanged: no byte
+ * of a host buffer written, no row appended. The column calls are positional like dds_col_read (liveness is
+ * ignored) and append canonical, live rows; columns over different moduli, rows past the end, capacity exceeded or
+ * `out` equal to a source: DDS_E_ARG before any GPU work. num == den and a == b are legal. count == 0: DDS_OK.
+ * With dds_ctx_set_timing on, the kernels' device time is added to total_ms. */
+/* out[i] = rows[i]^-1 mod N (BigInteger.modInverse), mod_bytes each. A row >= N: DDS_E_RANGE with *bad_row its
+ * index, checked on the big-endian bytes before any GPU work. */
+int dds_modinv_rows(dds_ctx*, const uint8_t* mod_be, size_t mod_bytes, const uint8_t* rows_be, size_t width,
+                    size_t count, uint8_t* out, size_t* bad_row);
+/* Enc(-m_i): append the inverses of rows [first, first+count) of `in` to `out`. */
+int dds_col_append_inv(dds_col* out, dds_col* in, size_t first, size_t count, size_t* bad_row);
+/* Enc(m_num - m_den): append num[num_first+i] * den[den_first+i]^-1 mod N. */
+int dds_col_append_quot(dds_col* out, dds_col* num, size_t num_first, dds_col* den, size_t den_first, size_t count,
+                        size_t* bad_row);
+/* Enc(m_a + m_b): append a[a_first+i] * b[b_first+i] mod N. */
+int dds_col_append_mul(dds_col* out, dds_col* a, size_t a_first, dds_col* b, size_t b_first, size_t count);
 
 /* ---- device-resident batched encryption (BASELINE.json config 4) --------------
  * dds_col_fill_random: append `count` seeded random rows r < 2^bits (odd, so r != 0):
