@@ -77,6 +77,36 @@ inline bn::Limbs lcg_odd(size_t bits, uint64_t seed) {
 
 inline bn::Limbs pow2m1(size_t k) { return bn::sub(bn::pow2(k), bn::Limbs{1}); }
 
+// The Montgomery product of the lane-group kernels (Mont::mul_col) for one modulus and one R = 2^k, at value
+// level: M(a, b) = (a·b + m·N)/R with m = -a·b/N mod R, so a·b·R⁻¹ mod N plus the multiple of N the kernels leave in
+// (inv_check.cpp, groups_check.cpp)
+struct MontR {
+  size_t k;  // R = 2^k
+  bn::Limbs N, N2, R, Rmod, nprime;
+  MontR(const bn::Limbs& N_, size_t k_) : k(k_), N(N_) {
+    N2 = bn::add(N, N);
+    R = bn::pow2(k);
+    need(bn::cmp(bn::add(N2, N2), R) < 0, "R > 4N");
+    Rmod = bn::mod(R, N);
+    nprime = bn::sub(R, bn::inv_mod_pow2(N, k));  // -N⁻¹ mod R
+    need(bn::low_bits(bn::add(bn::mul(N, nprime), bn::Limbs{1}), k).empty(), "N·n' != -1 mod R");
+  }
+  bn::Limbs M(const bn::Limbs& a, const bn::Limbs& b) const {
+    const bn::Limbs ab = bn::mul(a, b);
+    const bn::Limbs m = bn::low_bits(bn::mul(bn::low_bits(ab, k), nprime), k);
+    const bn::Limbs t = bn::add(ab, bn::mul(m, N));
+    need(bn::low_bits(t, k).empty(), "Montgomery product: a·b + m·N is no multiple of R");
+    bn::Limbs q;  // t >> k
+    for (size_t w = k / 32; w < t.size(); ++w) {
+      const uint64_t two = (uint64_t)t[w] | (w + 1 < t.size() ? (uint64_t)t[w + 1] << 32 : 0);
+      q.push_back((uint32_t)(two >> (k % 32)));
+    }
+    bn::trim(q);
+    return q;
+  }
+  bool below2N(const bn::Limbs& v) const { return bn::cmp(v, N2) < 0; }
+};
+
 // the committed 2048-bit Paillier key's n (tests/golden/keys.json, paillier2048_committed)
 inline const bn::Limbs kCommittedN = from_hex(
     "9bb877201eaff7b911662e986eef4a33cb9a83535b5a85820a8b9969ecffa2ab49fbb4d5cce1ab05d6804929e2eeaf76"

@@ -1,5 +1,5 @@
 // Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp, ddshe_opecol.cpp,
-// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp):
+// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp, ddshe_groups.cpp):
 // contexts, stream/buffer pools, per-modulus Montgomery constants, device columns and the
 // orchestration helpers around the HIP kernels. Not part of the public ABI (include/ddshe.h).
 #pragma once
@@ -107,6 +107,9 @@ struct Worker {
   DevBuf wf_w, wf_ids, wf_hist, wf_cnt, wf_list;
   // batched inversion (inv_device): the prefix products of a chunk's rows, the upper levels' planes
   DevBuf inv_pfx, inv_lv;
+  // grouped fold (ddshe_groups.cpp): the call's labels and row ids, group sizes, scan cursors and tile sums, the
+  // sorted id list, the levels' chunk descriptors, the two level buffers
+  DevBuf gp_lab, gp_ids, gp_cnt, gp_cur, gp_sums, gp_list, gp_desc, gp_buf[2];
   DevBuf crt[7];  // CRT scratch of Paillier encryption and decryption (encrypt_crt_device, decrypt_crt_device)
   hipEvent_t ev[4] = {};
   // decimal codec: double-buffered pinned chunks (chars, offsets), their device copies,
@@ -172,7 +175,11 @@ struct ModConsts {
   std::mutex decmu;
   uint32_t* dtab = nullptr;
   int jfit = 0, jpad = 0;
+  // grouped fold's constants (ddshe_groups_plan.hpp), built on first use: row k = R^k mod N, k = 0 .. F + 1
+  std::mutex gpmu;
+  uint32_t* dgtab = nullptr;
   ~ModConsts() {
+    if (dgtab) (void)hipFree(dgtab);
     if (d) (void)hipFree(d);
     if (d2) (void)hipFree(d2);
     if (dq) (void)hipFree(dq);

@@ -1,6 +1,6 @@
 // Internal launcher interface between the C-ABI's host code (ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp,
-// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp) and the
-// HIP kernels.
+// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp,
+// ddshe_groups.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -182,6 +182,25 @@ size_t wfold_blocks(size_t n);
 hipError_t launch_wfold_buckets(const int64_t* weights, const uint32_t* ids, uint32_t first, const uint8_t* live,
                                 size_t n, bool neg, uint32_t shift, int cbits, uint32_t* hist, uint32_t* counts,
                                 uint32_t* list, hipStream_t st);
+// Grouped fold (ddshe_groups.hip, ddshe_groups_plan.hpp). launch_grp_sort: the live items of [0, n) (row ids[i], or
+// first + i when ids is null; live[row] != 0, or live null; rows: the column's row count) sorted by labels[i] <
+// ngroups: cnt[g] = the size of group g, and the row ids of group 0, then 1, ... back to back in list (n words).
+// cnt, cur: ngroups words each; sums: grp_tiles(ngroups) words. n, ngroups in [1, 2^32 - 1].
+// launch_grp_fill_empty: the literal 1 into row g of O for every g with cnt[g] == 0.
+// launch_grp_fold: one level of the segmented fold over desc[0..nchunks) (host::GrpChunk). idx: inputs are the
+// rows list[.] of X (cap slots), else rows of X itself; xrows rows of X may be read; results to row dest < brows of
+// B (normalised, below 2N) or, final, to row dest < orows of O (canonical). tab: host::kGroupsTabRows rows R^k mod N
+// at stride host::kGroupsTabStride.
+size_t grp_tiles(size_t n);
+hipError_t launch_grp_sort(const uint32_t* labels, const uint32_t* ids, uint32_t first, const uint8_t* live,
+                           size_t rows, size_t n, size_t ngroups, uint32_t* cnt, uint32_t* cur, uint32_t* sums,
+                           uint32_t* list, hipStream_t st);
+hipError_t launch_grp_fill_empty(int S, const uint32_t* cnt, size_t ngroups, uint32_t* O, size_t ostride,
+                                 hipStream_t st);
+hipError_t launch_grp_fold(int S, bool idx, const uint32_t* X, size_t xstride, size_t xrows, const uint32_t* list,
+                           size_t cap, const void* desc, size_t nchunks, const uint32_t* consts, uint32_t n0,
+                           const uint32_t* tab, uint32_t* B, size_t bstride, size_t brows, uint32_t* O, size_t ostride,
+                           size_t orows, hipStream_t st);
 // Prime search (ddshe_prime.hpp). launch_strong1: lane t < nlanes tests row idx[t / rounds] (t / rounds when idx is
 // null) of Ncol (S1 = 20 | 40 | 56 limbs of 28 bits, odd, >= 3, at most nbits <= 28 S1 - 2 bits each) to base 2
 // (base2), to row t of Bcol, or with Bcol null to the witness of (seed, row, t % rounds), N >= 5; out[t] = 1 iff

@@ -35,34 +35,6 @@ constexpr ShapeRow kShapeRows[] = {{40, 2, 28},  {76, 2, 28},   {112, 4, 28}, {1
 
 Lcg g_rng{0x452821E638D01377ull};
 
-// the kernels' Montgomery product for one modulus and one R
-struct MontR {
-  size_t k;  // R = 2^k
-  bn::Limbs N, N2, R, Rmod, nprime;
-  MontR(const bn::Limbs& N_, size_t k_) : k(k_), N(N_) {
-    N2 = bn::add(N, N);
-    R = bn::pow2(k);
-    need(bn::cmp(bn::add(N2, N2), R) < 0, "R > 4N");
-    Rmod = bn::mod(R, N);
-    nprime = bn::sub(R, bn::inv_mod_pow2(N, k));  // -N⁻¹ mod R
-    need(bn::low_bits(bn::add(bn::mul(N, nprime), bn::Limbs{1}), k).empty(), "N·n' != -1 mod R");
-  }
-  bn::Limbs M(const bn::Limbs& a, const bn::Limbs& b) const {
-    const bn::Limbs ab = bn::mul(a, b);
-    const bn::Limbs m = bn::low_bits(bn::mul(bn::low_bits(ab, k), nprime), k);
-    const bn::Limbs t = bn::add(ab, bn::mul(m, N));
-    need(bn::low_bits(t, k).empty(), "Montgomery product: a·b + m·N is no multiple of R");
-    bn::Limbs q;  // t >> k
-    for (size_t w = k / 32; w < t.size(); ++w) {
-      const uint64_t two = (uint64_t)t[w] | (w + 1 < t.size() ? (uint64_t)t[w + 1] << 32 : 0);
-      q.push_back((uint32_t)(two >> (k % 32)));
-    }
-    bn::trim(q);
-    return q;
-  }
-  bool below2N(const bn::Limbs& v) const { return bn::cmp(v, N2) < 0; }
-};
-
 void check_plan(const InvPlan& pl, size_t rows, const std::string& tag) {
   const size_t nl = pl.levels();
   need(nl >= 1 && pl.cnt[0] == rows && pl.cnt[nl] <= kInvFan && pl.cnt[nl] >= 1, tag + "levels");

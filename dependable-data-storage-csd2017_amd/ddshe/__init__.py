@@ -72,6 +72,7 @@ EXPORTS = [
     "dds_modexp_rows", "dds_col_append_pow", "dds_exprows_plan", "dds_col_fold_weighted",
     "dds_col_fold_weighted_dec", "dds_fold_weighted_plan",
     "dds_modinv_rows", "dds_col_append_inv", "dds_col_append_quot", "dds_col_append_mul",
+    "dds_col_fold_groups", "dds_col_fold_groups_be", "dds_fold_groups_plan",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -184,6 +185,10 @@ _sig("dds_modinv_rows", C.c_int, C.c_void_p, C.c_char_p, _sz, C.c_char_p, _sz, _
 _sig("dds_col_append_inv", C.c_int, C.c_void_p, C.c_void_p, _sz, _sz, _szp)
 _sig("dds_col_append_quot", C.c_int, C.c_void_p, C.c_void_p, _sz, C.c_void_p, _sz, _sz, _szp)
 _sig("dds_col_append_mul", C.c_int, C.c_void_p, C.c_void_p, _sz, C.c_void_p, _sz, _sz)
+_u32p = C.POINTER(C.c_uint32)
+_sig("dds_col_fold_groups", C.c_int, C.c_void_p, _u64p, _sz, _sz, _u32p, _sz, C.c_void_p, _u64p)
+_sig("dds_col_fold_groups_be", C.c_int, C.c_void_p, _u64p, _sz, _sz, _u32p, _sz, _u8p, _u64p)
+_sig("dds_fold_groups_plan", C.c_int, _sz, _sz, C.POINTER(C.c_int), C.POINTER(C.c_int), _u64p, _u64p)
 _sig("dds_pair_modmul_dec", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _sz, _szp)
 _sig("dds_pair_stats", C.c_int, C.c_void_p, _u64p, _u64p)
 _sig("dds_pair_timing", C.c_int, C.c_void_p, _u64p, _u64p, _u64p, _u64p)
@@ -720,6 +725,15 @@ class Engine:
                "dds_fold_weighted_plan")
         return c.value, rp.value, hp.value
 
+    @staticmethod
+    def fold_groups_plan(n: int, max_group: int) -> tuple:
+        """dds_fold_groups_plan: (fan, levels, products, workspace rows) of a grouped fold of n rows whose largest
+        group has max_group rows. No GPU work."""
+        f, lv, pr, ws = C.c_int(), C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(_lib.dds_fold_groups_plan(n, max_group, C.byref(f), C.byref(lv), C.byref(pr), C.byref(ws)),
+               "dds_fold_groups_plan")
+        return f.value, lv.value, pr.value, ws.value
+
     def host_register(self, arr: np.ndarray):
         """dds_host_register: page-lock a reusable output array (results DMA'd straight into it)."""
         _check(_lib.dds_host_register(self._h, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "dds_host_register")
@@ -959,6 +973,40 @@ class Column(_Mutable):
                                               wts.ctypes.data_as(_i64p), window, out, cap, C.byref(olen)),
                "dds_col_fold_weighted_dec")
         return out.value.decode()
+
+    def _groups_args(self, groups, ngroups, row_ids, first, count):
+        labels = np.ascontiguousarray(groups, dtype=np.uint32)
+        if row_ids is None:
+            ids, n = None, len(self) - first if count is None else count
+        else:
+            ids = np.ascontiguousarray(row_ids, dtype=np.uint64)
+            n = len(ids)
+        if len(labels) != n:
+            raise ValueError("one label per listed row")
+        return labels, ids, n, np.zeros(max(1, ngroups), dtype=np.uint64)
+
+    def fold_groups(self, groups, ngroups: int, row_ids=None, first: int = 0, count: int | None = None):
+        """dds_col_fold_groups_be: the grouped SumAll / MultAll. groups[i] < ngroups labels the i-th listed row
+        (row_ids, or rows [first, first+count)); returns (values, counts): values[g] = the product mod N of the
+        live rows labelled g as a canonical residue (1 for a group without a live row), counts[g] (uint64) how
+        many rows that were."""
+        labels, ids, n, counts = self._groups_args(groups, ngroups, row_ids, first, count)
+        out = (C.c_uint8 * (self.mb * max(1, ngroups)))()
+        _check(_lib.dds_col_fold_groups_be(self._h, None if ids is None else ids.ctypes.data_as(_u64p), first, n,
+                                           labels.ctypes.data_as(_u32p), ngroups, out, counts.ctypes.data_as(_u64p)),
+               "dds_col_fold_groups_be")
+        raw = bytes(out)
+        return [int.from_bytes(raw[g * self.mb:(g + 1) * self.mb], "big") for g in range(ngroups)], counts[:ngroups]
+
+    def append_fold_groups(self, src: "Column", groups, ngroups: int, row_ids=None, first: int = 0,
+                           count: int | None = None) -> np.ndarray:
+        """dds_col_fold_groups: the same values of src's rows appended to this column, group g at the old
+        len(self) + g, canonical and live; returns the counts."""
+        labels, ids, n, counts = src._groups_args(groups, ngroups, row_ids, first, count)
+        _check(_lib.dds_col_fold_groups(src._h, None if ids is None else ids.ctypes.data_as(_u64p), first, n,
+                                        labels.ctypes.data_as(_u32p), ngroups, self._h,
+                                        counts.ctypes.data_as(_u64p)), "dds_col_fold_groups")
+        return counts[:ngroups]
 
     def fold_partial_device(self, d_partial: int, first: int = 0, count: int | None = None):
         """dds_col_fold_partial_device: the partial (partial_words u32) into device memory at d_partial."""

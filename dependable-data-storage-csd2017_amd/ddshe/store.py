@@ -377,6 +377,44 @@ class ResidentStore:
                 return got
         return routes.mult_all(self.eng, self.rows(), position, pubkey=pubkey)
 
+    def _fold_by(self, c: _CipherColumn | None, by_position: int, modulus: int) -> dict[str, str]:
+        """the grouped fold of column c: the rows its resident fold takes (c.live; a qualifying element that does
+        not parse answers 500 and no qualifying row 404, as _fold does) that also hold an element at by_position,
+        grouped by that element's text; every value a canonical residue, also a one-row group's"""
+        if c is None or modulus != c.modulus:
+            raise ServerError("no resident column at this position under this modulus")
+        if c.bad:
+            raise ServerError("NumberFormatException: a qualifying element is not an integer")
+        if c.nlive == 0:
+            raise NotFound()
+        rows = [int(r) for r in np.flatnonzero(c.live) if len(self.val[r]) > by_position]
+        code: dict[str, int] = {}
+        labels = [code.setdefault(_elem_str(self.val[r][by_position]), len(code)) for r in rows]
+        if not rows:
+            return {}
+        try:
+            vals, counts = c.col.fold_groups(labels, len(code), row_ids=rows)
+        except DDSError as e:
+            raise ServerError(str(e)) from e
+        return {text: str(vals[g]) for text, g in code.items() if counts[g]}
+
+    def sum_all_by(self, position: int, by_position: int, nsqr: str) -> dict[str, str]:
+        """SumAll per group: {text of the element at by_position: Enc(sum of the group's m) as decimal text} over
+        the rows sum_all(position, nsqr) folds that hold an element at by_position. One grouped fold on the GPU
+        (dds_col_fold_groups_be); there is no plain branch, so nsqr is required."""
+        x = _bigint(nsqr)
+        if x is None:
+            raise ServerError("NumberFormatException: nsqr")
+        return self._fold_by(self.by_pos_sum.get(position), by_position, x)
+
+    def mult_all_by(self, position: int, by_position: int, pubkey: str) -> dict[str, str]:
+        """MultAll per group, as sum_all_by, under the modulus of pubkey."""
+        try:
+            n = rsa_modulus(pubkey)
+        except ValueError as e:
+            raise ServerError(f"InvalidKeySpecException: {e}") from e
+        return self._fold_by(self.by_pos_mult.get(position), by_position, n)
+
     def search(self, route: str, position: int, value) -> list[str]:
         """POST /Search{Gt,GtEq,Lt,LtEq}?position (:682-830): matching keys in row order (the
         reference's order is unspecified). The match set comes back as a row bitmask."""

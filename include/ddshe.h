@@ -621,6 +621,43 @@ int dds_col_append_quot(dds_col* out, dds_col* num, size_t num_first, dds_col* d
 /* Enc(m_a + m_b): append a[a_first+i] * b[b_first+i] mod N. */
 int dds_col_append_mul(dds_col* out, dds_col* a, size_t a_first, dds_col* b, size_t b_first, size_t count);
 
+/* ---- grouped SumAll / MultAll: one fold per group, all groups at once ----------
+ * Grouped fold: out row g = prod of the live rows i of the call with groups[i] == g, mod N (Enc(sum of the group's
+ * m) for a Paillier column, the group's MultAll for an RSA one). The live rows are sorted by label on the GPU (a
+ * counting sort; counters in LDS up to 256 groups, in global memory above) and every segment is folded 32 rows per
+ * lane group and level: the launches and the two host synchronisations of a call depend on
+ * ceil(log_32(largest group)) only, never on ngroups, and one huge group beside many tiny ones still spreads over
+ * the device. Any odd modulus of the lane-group shapes; the opaque rows only (the digit mirror is neither used nor
+ * touched).
+ * Rows are row_ids[0..n), or [first, first+n) when row_ids is NULL; groups[i] belongs to the i-th listed row; a row
+ * id listed twice contributes twice; dead rows drop out together with their labels. counts (nullable, ngroups
+ * entries) receives the number of live rows folded into each group. Every value is the canonical residue in [0, N),
+ * for a one-row group too (not dds_col_fold's "operand as appended"). A group with no live row has the value 1
+ * (the empty product, Enc(0) with r = 1) and count 0: the caller maps count 0 to the route's 404. A call with no
+ * live row at all, and n == 0 with ngroups > 0, is DDS_OK with every count 0. ngroups == 0: DDS_OK, nothing is read
+ * or written.
+ * All checks run before any GPU work, and on any error out and counts are untouched (no row appended). DDS_E_ARG: a
+ * NULL col or out, a NULL groups when n > 0, a label >= ngroups (dds_last_error names the index), a row id out of
+ * range or rows past the end, out == col, columns over different moduli, out's capacity exceeded.
+ * DDS_E_UNSUPPORTED: n or ngroups above 2^32 - 1 (_be: ngroups above the row limit of one column). A workspace allocation that fails: DDS_E_NOMEM, nothing appended.
+ * Thread-safe on one context, on a stream of its pool, no exception crosses. With dds_ctx_set_timing on, the
+ * grouping kernels add to total_ms and the fold levels to fold_ms. */
+/* Column form: appends ngroups canonical, live rows to out, row g at old count + g (they stay resident for
+ * dds_col_decrypt_paillier, dds_col_read_dec, dds_col_append_quot, ...). out is locked exclusively, col shared. */
+int dds_col_fold_groups(dds_col* col, const uint64_t* row_ids, size_t first, size_t n, const uint32_t* groups,
+                        size_t ngroups, dds_col* out, uint64_t* counts);
+/* The same values as big-endian rows of the column's modulus width: out holds ngroups * mod_bytes bytes. */
+int dds_col_fold_groups_be(dds_col* col, const uint64_t* row_ids, size_t first, size_t n, const uint32_t* groups,
+                           size_t ngroups, uint8_t* out, uint64_t* counts);
+/* What the segmented fold does for n rows whose largest group has max_group rows (1 <= max_group <= n, or both 0;
+ * else DDS_E_ARG): the fan (rows per lane group and level), the fold levels = launches of the largest group, the
+ * Montgomery products for n rows in groups of max_group rows each (the last one the remainder): rows - groups,
+ * plus one product with a constant per level-1 chunk (none for a one-row group) and one per group that needs a
+ * second level; and an upper bound of the scratch rows (beyond out) for any labeling with that largest group,
+ * at most 2n/33. Every output is nullable. No GPU work. */
+int dds_fold_groups_plan(size_t n, size_t max_group, int* fan, int* levels, uint64_t* products,
+                         uint64_t* workspace_rows);
+
 /* ---- device-resident batched encryption (BASELINE.json config 4) --------------
  * dds_col_fill_random: append `count` seeded random rows r < 2^bits (odd, so r != 0):
  *   limb l of row i = splitmix64(splitmix64(seed ^ (row0+i)) + l) in the column's rW layout.
