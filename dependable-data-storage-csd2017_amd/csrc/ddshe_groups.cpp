@@ -5,6 +5,9 @@
 // (ddshe_groups_plan.hpp), and k_grp_fold (ddshe_groups.hpp) runs once per level: ceil(log_F(largest group))
 // launches and two synchronisations, whatever the number of groups. The opaque gather path only: it reads col->d
 // and neither uses nor touches the digit mirror.
+// Also here: the dense ranks of a key column (dds_ope_rank[_device], kernels in ddshe_rank.hip) and the grouped fold
+// keyed by a resident OPE column (dds_col_fold_by_ope[_be]), whose labels never leave the device: the stable sort's
+// permutation, cut where the key changes, is the same id list, and fold_segments runs the levels for both.
 #include "ddshe_groups_plan.hpp"
 #include "ddshe_host.hpp"
 
@@ -43,6 +46,59 @@ int groups_table(ModConsts& mc) {
     return fail(DDS_E_HIP, std::string("grouped fold table: ") + hipGetErrorString(e));
   }
   mc.dgtab = d;
+  return DDS_OK;
+}
+
+// The segmented fold itself: segment g of list[0..cap) holds counts[g] row ids of the column, segment after segment;
+// row g of O (stride ostride, not overlapping the column) <- the canonical product of segment g's rows, the
+// literal 1 for an empty one (d_cnt: the counts on the device, read only then). The caller holds col->mu.
+// Synchronises the stream. With timing on, the levels add to fold_ms, fold_launches and fold_modmuls.
+int fold_segments(dds_col* col, Worker* w, hipStream_t st, const uint32_t* d_list, size_t cap, const uint32_t* counts,
+                  const uint32_t* d_cnt, size_t ngroups, uint32_t* O, size_t ostride) {
+  dds_ctx* ctx = col->ctx;
+  ModConsts& mc = *col->mc;
+  const int S = mc.S;
+  const bool timed = ctx->timing.load();
+  const GroupsPlan pl(counts, ngroups);
+  if (pl.rows > cap) return fail(DDS_E_HIP, "group sizes exceed the call's rows");
+  size_t bstride[2], nchunks = 0;
+  for (int b = 0; b < 2; ++b) {
+    bstride[b] = round_up(pl.buf_rows[b], 64);
+    if (bstride[b] > max_stride(S)) return fail(DDS_E_UNSUPPORTED, "level buffer exceeds the row limit of this modulus");
+    if (bstride[b]) GRP_ALLOC(w->gp_buf[b].ensure((size_t)S * bstride[b] * 4));
+  }
+  for (const GroupsLevel& lv : pl.levels) nchunks += lv.chunks.size();
+  std::vector<GrpChunk> desc;
+  desc.reserve(nchunks);
+  for (const GroupsLevel& lv : pl.levels) desc.insert(desc.end(), lv.chunks.begin(), lv.chunks.end());
+  if (nchunks) {
+    GRP_ALLOC(w->gp_desc.ensure(nchunks * sizeof(GrpChunk)));
+    HIP_TRY(hipMemcpyAsync(w->gp_desc.p, desc.data(), nchunks * sizeof(GrpChunk), hipMemcpyHostToDevice, st));
+  }
+  if (pl.nonempty < ngroups) HIP_TRY(launch_grp_fill_empty(S, d_cnt, ngroups, O, ostride, st));
+  if (timed) HIP_TRY(hipEventRecord(w->ev[0], st));
+  size_t at = 0;
+  for (size_t i = 0; i < pl.levels.size(); ++i) {
+    const GroupsLevel& lv = pl.levels[i];
+    const bool idx = i == 0;
+    const size_t ib = (i + 1) % 2, ob = i % 2;  // level i reads what level i - 1 stored
+    HIP_TRY(launch_grp_fold(S, idx, idx ? col->d : w->gp_buf[ib].as<uint32_t>(), idx ? col->stride : bstride[ib],
+                            idx ? col->count : lv.in_rows, d_list, pl.rows, w->gp_desc.as<GrpChunk>() + at,
+                            lv.chunks.size(), mc.d, mc.n0, mc.dgtab,
+                            lv.out_rows ? w->gp_buf[ob].as<uint32_t>() : nullptr, bstride[ob], lv.out_rows, O, ostride,
+                            ngroups, st));
+    at += lv.chunks.size();
+  }
+  if (timed) HIP_TRY(hipEventRecord(w->ev[1], st));
+  HIP_TRY(hipStreamSynchronize(st));  // desc goes; the rows of O are complete
+  if (timed) {
+    float fold_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&fold_ms, w->ev[0], w->ev[1]));
+    std::lock_guard<std::mutex> lk(ctx->tmu);
+    ctx->fold_ms += fold_ms;
+    ctx->fold_launches += pl.levels.size();
+    ctx->fold_modmuls += pl.products;
+  }
   return DDS_OK;
 }
 
@@ -104,47 +160,13 @@ int fold_groups_device(dds_col* col, Worker* w, hipStream_t st, const uint64_t* 
   HIP_TRY(hipMemcpyAsync(counts->data(), d_cnt, ngroups * 4, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));  // the sizes are here; the caller's arrays and ids32 are free again
 
-  const GroupsPlan pl(counts->data(), ngroups);
-  if (pl.rows > n) return fail(DDS_E_HIP, "group sizes exceed the call's rows");
-  size_t bstride[2], nchunks = 0;
-  for (int b = 0; b < 2; ++b) {
-    bstride[b] = round_up(pl.buf_rows[b], 64);
-    if (bstride[b] > max_stride(S)) return fail(DDS_E_UNSUPPORTED, "level buffer exceeds the row limit of this modulus");
-    if (bstride[b]) GRP_ALLOC(w->gp_buf[b].ensure((size_t)S * bstride[b] * 4));
-  }
-  for (const GroupsLevel& lv : pl.levels) nchunks += lv.chunks.size();
-  std::vector<GrpChunk> desc;
-  desc.reserve(nchunks);
-  for (const GroupsLevel& lv : pl.levels) desc.insert(desc.end(), lv.chunks.begin(), lv.chunks.end());
-  if (nchunks) {
-    GRP_ALLOC(w->gp_desc.ensure(nchunks * sizeof(GrpChunk)));
-    HIP_TRY(hipMemcpyAsync(w->gp_desc.p, desc.data(), nchunks * sizeof(GrpChunk), hipMemcpyHostToDevice, st));
-  }
-  if (pl.nonempty < ngroups) HIP_TRY(launch_grp_fill_empty(S, d_cnt, ngroups, O, ostride, st));
-  if (timed) HIP_TRY(hipEventRecord(w->ev[0], st));
-  size_t at = 0;
-  for (size_t i = 0; i < pl.levels.size(); ++i) {
-    const GroupsLevel& lv = pl.levels[i];
-    const bool idx = i == 0;
-    const size_t ib = (i + 1) % 2, ob = i % 2;  // level i reads what level i - 1 stored
-    HIP_TRY(launch_grp_fold(S, idx, idx ? col->d : w->gp_buf[ib].as<uint32_t>(), idx ? col->stride : bstride[ib],
-                            idx ? col->count : lv.in_rows, w->gp_list.as<uint32_t>(), pl.rows,
-                            w->gp_desc.as<GrpChunk>() + at, lv.chunks.size(), mc.d, mc.n0, mc.dgtab,
-                            lv.out_rows ? w->gp_buf[ob].as<uint32_t>() : nullptr, bstride[ob], lv.out_rows, O, ostride,
-                            ngroups, st));
-    at += lv.chunks.size();
-  }
-  if (timed) HIP_TRY(hipEventRecord(w->ev[1], st));
-  HIP_TRY(hipStreamSynchronize(st));  // desc goes; the rows of O are complete
+  if ((rc = fold_segments(col, w, st, w->gp_list.as<uint32_t>(), n, counts->data(), d_cnt, ngroups, O, ostride)))
+    return rc;
   if (timed) {
-    float sort_ms = 0, fold_ms = 0;
+    float sort_ms = 0;
     HIP_TRY(hipEventElapsedTime(&sort_ms, w->ev[2], w->ev[3]));
-    HIP_TRY(hipEventElapsedTime(&fold_ms, w->ev[0], w->ev[1]));
     std::lock_guard<std::mutex> lk(ctx->tmu);
     ctx->total_ms += sort_ms;
-    ctx->fold_ms += fold_ms;
-    ctx->fold_launches += pl.levels.size();
-    ctx->fold_modmuls += pl.products;
   }
   return DDS_OK;
 }
@@ -160,6 +182,133 @@ int fold_groups_args(const dds_col* col, size_t n, const uint32_t* groups, size_
 void give_counts(const std::vector<uint32_t>& c, uint64_t* counts) {
   if (counts)
     for (size_t g = 0; g < c.size(); ++g) counts[g] = c[g];
+}
+
+// Dense ranks of the n >= 1 device keys d_col among the rows with d_valid[i] != 0 (null: every row): the stable
+// ascending sort into w->rk_perm (invalid rows first), then the rank kernels; *ngroups <- the distinct keys, read
+// back in one small copy. d_labels, d_keys: nullable. With ngroups > 0 and want_counts the group sizes go to
+// d_counts, or to w->gp_cnt when that is null (*counts_out names the array). The segment starts stay in
+// w->rk_start. Synchronises the stream once; the counts kernel is only enqueued.
+int rank_device(Worker* w, hipStream_t st, const int64_t* d_col, const uint8_t* d_valid, size_t n,
+                const uint64_t* ubounds, uint32_t* d_labels, int64_t* d_keys, bool want_counts, uint32_t* d_counts,
+                size_t* ngroups, const uint32_t** counts_out) {
+  const size_t nt = rank_tiles(n);
+  GRP_ALLOC(w->tab.ensure(rs_scratch_bytes(n)));
+  GRP_ALLOC(w->rk_perm.ensure(n * 4));
+  GRP_ALLOC(w->rk_sums.ensure((nt + 1) * 4));
+  GRP_ALLOC(w->rk_start.ensure(n * 4));
+  MappedWords ow;
+  HIP_TRY(mapped_words(w, &ow));
+  HIP_TRY(launch_ope_order(d_col, d_valid, n, 0, w->tab.p, w->rk_perm.as<uint32_t>(), st, ubounds, &ow));
+  HIP_TRY(launch_ope_rank(d_col, d_valid, w->rk_perm.as<uint32_t>(), n, w->rk_sums.as<uint32_t>(), d_labels, d_keys,
+                          w->rk_start.as<uint32_t>(), st));
+  uint32_t ng = 0;
+  HIP_TRY(read_sync(w, st, w->rk_sums.as<uint32_t>() + nt, &ng, 4));
+  if (ng > n) return fail(DDS_E_HIP, "more distinct keys than rows");
+  *ngroups = ng;
+  if (counts_out) *counts_out = nullptr;
+  if (ng && want_counts) {
+    if (!d_counts) {
+      GRP_ALLOC(w->gp_cnt.ensure((size_t)ng * 4));
+      d_counts = w->gp_cnt.as<uint32_t>();
+    }
+    HIP_TRY(launch_rank_counts(w->rk_start.as<uint32_t>(), ng, n, d_counts, st));
+    if (counts_out) *counts_out = d_counts;
+  }
+  return DDS_OK;
+}
+
+// what both rank entry points refuse before any GPU work; *ngroups = 0
+int rank_args(dds_ctx* ctx, const void* col, size_t n, size_t* ngroups) {
+  if (!ctx || !ngroups || (n && !col)) return fail(DDS_E_ARG, "bad arguments");
+  *ngroups = 0;
+  if (n > (size_t)0xFFFFFFFFu) return fail(DDS_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");  // 32-bit slots
+  return DDS_OK;
+}
+
+// The grouped fold of `col` keyed by the resident OPE column K (dds_col_fold_by_ope[_be]); the caller holds both
+// columns' locks and has checked the arguments. The valid kernel, the sort and the rank kernels label the rows on the
+// device; the sorted permutation's valid tail is the segmented fold's id list as it stands. *ngroups <- the
+// distinct keys among the participating rows; above cap: DDS_E_BUFSIZE before anything is written. dest(ngroups, &O,
+// &ostride) then names the rows the values go to (or fails). hkeys / hcounts: filled on success only.
+template <class Dest>
+int fold_by_ope_device(dds_col* col, const OpeKeys& K, Worker* w, hipStream_t st, const uint64_t* mask, size_t cap,
+                       size_t* ngroups, std::vector<int64_t>* hkeys, std::vector<uint32_t>* hcounts, Dest dest) {
+  dds_ctx* ctx = col->ctx;
+  const size_t n = K.count, words = (n + 63) / 64;
+  int rc;
+  if ((rc = groups_table(*col->mc))) return rc;
+  GRP_ALLOC(w->rk_valid.ensure(n));
+  GRP_ALLOC(w->rk_keys.ensure(n * 8));
+  const uint64_t* d_mask = nullptr;
+  if (mask) {
+    GRP_ALLOC(w->rk_mask.ensure(words * 8));
+    HIP_TRY(hipMemcpyAsync(w->rk_mask.p, mask, words * 8, hipMemcpyHostToDevice, st));  // one bit per row
+    d_mask = w->rk_mask.as<uint64_t>();
+  }
+  const bool timed = ctx->timing.load();
+  if (timed) HIP_TRY(hipEventRecord(w->ev[2], st));
+  HIP_TRY(launch_by_valid(K.d_cls, K.hold, K.d_dead, col->ndead ? col->dlive : nullptr, d_mask, n,
+                          w->rk_valid.as<uint8_t>(), st));
+  size_t ng = 0;
+  const uint32_t* d_cnt = nullptr;
+  if ((rc = rank_device(w, st, K.d_val, w->rk_valid.as<uint8_t>(), n, K.ubounds, nullptr, w->rk_keys.as<int64_t>(),
+                        true, nullptr, &ng, &d_cnt)))
+    return rc;
+  if (timed) HIP_TRY(hipEventRecord(w->ev[3], st));
+  *ngroups = ng;
+  if (ng > cap) {
+    HIP_TRY(hipStreamSynchronize(st));  // the counts kernel is done with the worker's buffers
+    return fail(DDS_E_BUFSIZE, std::to_string(ng) + " groups, room for " + std::to_string(cap));
+  }
+  if (ng == 0) return DDS_OK;
+  // keys and sizes through the pinned read-back buffer, one after the other
+  GRP_ALLOC(w->hbig.ensure(ng * 12));
+  int64_t* pk = (int64_t*)w->hbig.p;
+  uint32_t* pc = (uint32_t*)(pk + ng);
+  HIP_TRY(hipMemcpyAsync(pk, w->rk_keys.p, ng * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(pc, d_cnt, ng * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  hkeys->assign(pk, pk + ng);
+  hcounts->assign(pc, pc + ng);
+  size_t nvalid = 0;
+  for (uint32_t c : *hcounts) nvalid += c;
+  if (nvalid > n) return fail(DDS_E_HIP, "group sizes exceed the column's rows");
+  uint32_t* O = nullptr;
+  size_t ostride = 0;
+  if ((rc = dest(ng, &O, &ostride))) return rc;
+  // the invalid rows come first in the permutation: the participating ones are its last nvalid slots
+  if ((rc = fold_segments(col, w, st, w->rk_perm.as<uint32_t>() + (n - nvalid), nvalid, hcounts->data(), d_cnt, ng, O,
+                          ostride)))
+    return rc;
+  if (timed) {
+    float label_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&label_ms, w->ev[2], w->ev[3]));
+    std::lock_guard<std::mutex> lk(ctx->tmu);
+    ctx->total_ms += label_ms;
+  }
+  return DDS_OK;
+}
+
+// what both keyed entry points refuse before they look at a column
+int fold_by_ope_args(const dds_col* col, const dds_opecol* by, const size_t* ngroups) {
+  if (!col || !by || !ngroups) return fail(DDS_E_ARG, "bad arguments");
+  return DDS_OK;
+}
+
+// the checks that need the two columns; the caller holds both locks
+int fold_by_ope_rows(const dds_col* col, const OpeKeys& K, const uint64_t* mask, size_t mask_words) {
+  if (K.ctx != col->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
+  if (K.count != col->count) return fail(DDS_E_ARG, "the key column and the folded column differ in rows");
+  if (mask && mask_words < (K.count + 63) / 64) return fail(DDS_E_ARG, "mask needs ceil(count / 64) words");
+  if (K.n_bad) return fail(DDS_E_FORMAT, "NumberFormatException: a live key element is not an integer");
+  if (K.n_wide) return fail(DDS_E_UNSUPPORTED, "a live key element is outside int64");
+  return DDS_OK;
+}
+
+void give_keys(const std::vector<int64_t>& k, const std::vector<uint32_t>& c, int64_t* keys, uint64_t* counts) {
+  if (keys) std::copy(k.begin(), k.end(), keys);
+  give_counts(c, counts);
 }
 
 }  // namespace
@@ -231,6 +380,134 @@ int dds_col_fold_groups_be(dds_col* col, const uint64_t* row_ids, size_t first, 
       return rc;
     if ((rc = rows_to_be(w, wl.st, mc, w->x.as<uint32_t>(), stride, ngroups, false, out, mc.bytes))) return rc;
     give_counts(c, counts);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_ope_rank_device(dds_ctx* ctx, const int64_t* d_col, const uint8_t* d_valid, size_t n, uint32_t* d_labels,
+                        int64_t* d_keys, uint32_t* d_counts, size_t* ngroups) {
+  try {
+    int rc = rank_args(ctx, d_col, n, ngroups);
+    if (rc || n == 0) return rc;
+    WorkerLease wl(ctx);
+    if ((rc = wl.acquire())) return rc;
+    if ((rc = rank_device(wl.w, wl.st, d_col, d_valid, n, nullptr, d_labels, d_keys, d_counts != nullptr, d_counts,
+                          ngroups, nullptr)))
+      return rc;
+    HIP_TRY(hipStreamSynchronize(wl.st));
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_ope_rank(dds_ctx* ctx, const int64_t* col, const uint8_t* valid, size_t n, uint32_t* labels, int64_t* keys,
+                 uint64_t* counts, size_t* ngroups) {
+  try {
+    int rc = rank_args(ctx, col, n, ngroups);
+    if (rc || n == 0) return rc;
+    WorkerLease wl(ctx);
+    if ((rc = wl.acquire())) return rc;
+    Worker* w = wl.w;
+    GRP_ALLOC(w->in.ensure(n * 8));
+    if (valid) GRP_ALLOC(w->in2.ensure(n));
+    if (labels) GRP_ALLOC(w->rk_lab.ensure(n * 4));
+    if (keys) GRP_ALLOC(w->rk_keys.ensure(n * 8));
+    HIP_TRY(hipMemcpyAsync(w->in.p, col, n * 8, hipMemcpyHostToDevice, wl.st));
+    if (valid) HIP_TRY(hipMemcpyAsync(w->in2.p, valid, n, hipMemcpyHostToDevice, wl.st));
+    size_t ng = 0;
+    const uint32_t* d_cnt = nullptr;
+    if ((rc = rank_device(w, wl.st, w->in.as<int64_t>(), valid ? w->in2.as<uint8_t>() : nullptr, n, nullptr,
+                          labels ? w->rk_lab.as<uint32_t>() : nullptr, keys ? w->rk_keys.as<int64_t>() : nullptr,
+                          counts != nullptr, nullptr, &ng, &d_cnt)))
+      return rc;
+    std::vector<uint32_t> c(counts ? ng : 0);
+    if (labels) HIP_TRY(hipMemcpyAsync(labels, w->rk_lab.p, n * 4, hipMemcpyDeviceToHost, wl.st));
+    if (keys && ng) HIP_TRY(hipMemcpyAsync(keys, w->rk_keys.p, ng * 8, hipMemcpyDeviceToHost, wl.st));
+    if (counts && ng) HIP_TRY(hipMemcpyAsync(c.data(), d_cnt, ng * 4, hipMemcpyDeviceToHost, wl.st));
+    HIP_TRY(hipStreamSynchronize(wl.st));
+    give_counts(c, counts);
+    *ngroups = ng;
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_fold_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, dds_col* out,
+                        int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups) {
+  try {
+    int rc = fold_by_ope_args(col, by, ngroups);
+    if (rc) return rc;
+    *ngroups = 0;
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    if (out == col) return fail(DDS_E_ARG, "out and the source column must differ");
+    ColWriteLock lk(out, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lr(col->mu, std::defer_lock);  // `col` and `by` are only read
+    std::shared_lock<std::shared_mutex> lb(opecol_mutex(by), std::defer_lock);
+    std::lock(lk.lk, lr, lb);
+    lk.touches_from(out->count);  // an append
+    if (col->ctx != out->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
+    if (bn::cmp(out->mc->N, col->mc->N) != 0 || out->mc->S != col->mc->S || out->mc->W != col->mc->W)
+      return fail(DDS_E_ARG, "columns must be over the same modulus");
+    const OpeKeys K = opecol_keys(by);
+    if ((rc = fold_by_ope_rows(col, K, mask, mask_words))) return rc;
+    if (K.count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    std::vector<int64_t> k;
+    std::vector<uint32_t> c;
+    // rows past the count: nothing is published unless the call succeeds
+    auto dest = [&](size_t ng, uint32_t** O, size_t* ostride) {
+      if (ng > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
+      *O = out->d + out->count;
+      *ostride = out->stride;
+      return (int)DDS_OK;
+    };
+    if ((rc = fold_by_ope_device(col, K, wl.w, wl.st, mask, cap, ngroups, &k, &c, dest))) return rc;
+    out->count += *ngroups;
+    give_keys(k, c, keys, counts);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_fold_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, uint8_t* out,
+                           int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups) {
+  try {
+    int rc = fold_by_ope_args(col, by, ngroups);
+    if (rc) return rc;
+    *ngroups = 0;
+    if (cap && !out) return fail(DDS_E_ARG, "bad arguments");
+    std::shared_lock<std::shared_mutex> lr(col->mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lb(opecol_mutex(by), std::defer_lock);
+    std::lock(lr, lb);
+    ModConsts& mc = *col->mc;
+    const OpeKeys K = opecol_keys(by);
+    if ((rc = fold_by_ope_rows(col, K, mask, mask_words))) return rc;
+    if (K.count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    Worker* w = wl.w;
+    std::vector<int64_t> k;
+    std::vector<uint32_t> c;
+    size_t stride = 0;
+    auto dest = [&](size_t ng, uint32_t** O, size_t* ostride) {
+      int r = check_rows(mc, ng);
+      if (r) return r;
+      stride = round_up(ng, 64);
+      GRP_ALLOC(w->x.ensure((size_t)mc.S * stride * 4));
+      *O = w->x.as<uint32_t>();
+      *ostride = stride;
+      return (int)DDS_OK;
+    };
+    if ((rc = fold_by_ope_device(col, K, w, wl.st, mask, cap, ngroups, &k, &c, dest))) return rc;
+    if (*ngroups == 0) return DDS_OK;
+    if ((rc = rows_to_be(w, wl.st, mc, w->x.as<uint32_t>(), stride, *ngroups, false, out, mc.bytes))) return rc;
+    give_keys(k, c, keys, counts);
     return DDS_OK;
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");

@@ -110,6 +110,9 @@ struct Worker {
   // grouped fold (ddshe_groups.cpp): the call's labels and row ids, group sizes, scan cursors and tile sums, the
   // sorted id list, the levels' chunk descriptors, the two level buffers
   DevBuf gp_lab, gp_ids, gp_cnt, gp_cur, gp_sums, gp_list, gp_desc, gp_buf[2];
+  // dense ranks (ddshe_rank.hip): the sorted permutation, the tiles' head counts, the segment starts, the distinct
+  // keys, the labels, and for dds_col_fold_by_ope the valid bytes and the caller's row mask
+  DevBuf rk_perm, rk_sums, rk_start, rk_keys, rk_lab, rk_valid, rk_mask;
   DevBuf crt[7];  // CRT scratch of Paillier encryption and decryption (encrypt_crt_device, decrypt_crt_device)
   hipEvent_t ev[4] = {};
   // decimal codec: double-buffered pinned chunks (chars, offsets), their device copies,
@@ -740,6 +743,22 @@ int col_write_prepare(dds_col* col, const uint64_t* ids, size_t n, const uint8_t
                       const char* chars, const uint64_t* offsets, RowWrite* plan);
 int col_write_commit(dds_col* col, RowWrite& plan);
 int col_set_live(dds_col* col, const uint64_t* ids, size_t n, const uint8_t* live);
+// What dds_col_fold_by_ope (ddshe_groups.cpp) reads of a resident OPE column (ddshe_opecol.cpp): opecol_mutex is
+// the column's lock; opecol_keys, called with it held (shared), gives the device arrays (d_dead null: no removed
+// set yet), the bounds of the stored values in unsigned order (launch_ope_order's ubounds) and the live holders
+// whose element is malformed / outside int64.
+struct OpeKeys {
+  dds_ctx* ctx = nullptr;
+  size_t count = 0;
+  const int64_t* d_val = nullptr;
+  const uint8_t* d_cls = nullptr;
+  const uint8_t* d_dead = nullptr;
+  uint32_t hold = 0;  // the class bit "holds the position"
+  uint64_t ubounds[2] = {0, 0};
+  size_t n_bad = 0, n_wide = 0;
+};
+std::shared_mutex& opecol_mutex(dds_opecol* col);
+OpeKeys opecol_keys(const dds_opecol* col);
 int combine_partials(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, const uint32_t* h_parts,
                      const uint32_t* d_parts, const uint64_t* rows, size_t nparts, uint8_t* out, size_t out_cap,
                      size_t* out_len);

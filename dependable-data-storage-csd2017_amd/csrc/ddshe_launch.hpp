@@ -285,6 +285,22 @@ struct MappedWords {
 hipError_t launch_ope_order(const int64_t* col, const uint8_t* valid, size_t n, int desc, void* scratch,
                             uint32_t* out_ids, hipStream_t st, const uint64_t* ubounds = nullptr,
                             const MappedWords* hw = nullptr);
+// Dense ranks of a key column (ddshe_rank.hip), from perm = launch_ope_order's ascending permutation of the same
+// col / valid / n: labels[r] (nullable, n words) = the rank of row r's key among the distinct keys of the valid rows,
+// kRankNone for an invalid row; keys[g] (nullable, n entries) = the g-th distinct key; starts[g] (n words) = the
+// slot of perm where group g begins, its rows being perm[starts[g] .. starts[g + 1]) in ascending row order.
+// sums: rank_tiles(n) + 1 words; after the call sums[rank_tiles(n)] = the number of distinct keys. n in
+// [1, 2^32 - 1]. launch_rank_counts: counts[g] = the rows of group g, for that number of groups (>= 1).
+// launch_by_valid: valid[r] = (cls[r] & hold) != 0 and bdead[r] == 0 and clive[r] != 0 and bit r of mask (bdead,
+// clive, mask nullable: no such condition).
+constexpr int kRankTile = 4096;  // slots per block of the rank kernels' scan
+constexpr uint32_t kRankNone = 0xFFFFFFFFu;
+size_t rank_tiles(size_t n);
+hipError_t launch_ope_rank(const int64_t* col, const uint8_t* valid, const uint32_t* perm, size_t n, uint32_t* sums,
+                           uint32_t* labels, int64_t* keys, uint32_t* starts, hipStream_t st);
+hipError_t launch_rank_counts(const uint32_t* starts, size_t ngroups, size_t n, uint32_t* counts, hipStream_t st);
+hipError_t launch_by_valid(const uint8_t* cls, uint32_t hold, const uint8_t* bdead, const uint8_t* clive,
+                           const uint64_t* mask, size_t n, uint8_t* valid, hipStream_t st);
 // deterministic-equality scans (ddshe_strscan.hip)
 // 64-bit digest of an element string (FNV-1a over the bytes, splitmix finaliser); identical on
 // host (needles) and device (table). The table keeps its top 16 bits as a per-element fingerprint

@@ -53,6 +53,9 @@ struct dds_opecol {
   size_t n_search = 0, n_hold = 0;
   size_t n_search_bad = 0;  // kSearch rows that Search's BigInteger parse rejects
   size_t n_hold_bad = 0;    // kHold rows that Order's asInstanceOf[String].toLong rejects
+  // kHold rows whose element is no decimal integer / a decimal integer outside int64: dds_col_fold_by_ope groups
+  // by value, so a non-String element is fine there and these two answer differently
+  size_t n_key_bad = 0, n_key_wide = 0;
   ~dds_opecol() {
     if (d_val) (void)hipFree(d_val);
     if (d_flg) (void)hipFree(d_flg);
@@ -68,8 +71,33 @@ struct dds_opecol {
     upd(n_hold, f & kHold);
     upd(n_search_bad, (f & kSearch) && (f & kBad));
     upd(n_hold_bad, (f & kHold) && (f & (kBad | kWide | kNotStr)));
+    upd(n_key_bad, (f & kHold) && (f & kBad));
+    upd(n_key_wide, (f & kHold) && (f & kWide));
   }
 };
+
+namespace ddshe {
+namespace host {
+
+std::shared_mutex& opecol_mutex(dds_opecol* col) { return col->mu; }
+
+OpeKeys opecol_keys(const dds_opecol* col) {
+  OpeKeys k;
+  k.ctx = col->ctx;
+  k.count = col->count;
+  k.d_val = col->d_val;
+  k.d_cls = col->d_flg;
+  k.d_dead = col->ndead ? col->d_dead : nullptr;
+  k.hold = kHold;
+  k.ubounds[0] = col->ulo;
+  k.ubounds[1] = col->uhi;
+  k.n_bad = col->n_key_bad;
+  k.n_wide = col->n_key_wide;
+  return k;
+}
+
+}  // namespace host
+}  // namespace ddshe
 
 namespace {
 

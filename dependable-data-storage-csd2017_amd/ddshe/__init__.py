@@ -73,6 +73,7 @@ EXPORTS = [
     "dds_col_fold_weighted_dec", "dds_fold_weighted_plan",
     "dds_modinv_rows", "dds_col_append_inv", "dds_col_append_quot", "dds_col_append_mul",
     "dds_col_fold_groups", "dds_col_fold_groups_be", "dds_fold_groups_plan",
+    "dds_ope_rank", "dds_ope_rank_device", "dds_col_fold_by_ope", "dds_col_fold_by_ope_be",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -189,6 +190,10 @@ _u32p = C.POINTER(C.c_uint32)
 _sig("dds_col_fold_groups", C.c_int, C.c_void_p, _u64p, _sz, _sz, _u32p, _sz, C.c_void_p, _u64p)
 _sig("dds_col_fold_groups_be", C.c_int, C.c_void_p, _u64p, _sz, _sz, _u32p, _sz, _u8p, _u64p)
 _sig("dds_fold_groups_plan", C.c_int, _sz, _sz, C.POINTER(C.c_int), C.POINTER(C.c_int), _u64p, _u64p)
+_sig("dds_ope_rank", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _u32p, _i64p, _u64p, _szp)
+_sig("dds_ope_rank_device", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _szp)
+_sig("dds_col_fold_by_ope", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_void_p, _i64p, _u64p, _sz, _szp)
+_sig("dds_col_fold_by_ope_be", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, _u8p, _i64p, _u64p, _sz, _szp)
 _sig("dds_pair_modmul_dec", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _sz, _szp)
 _sig("dds_pair_stats", C.c_int, C.c_void_p, _u64p, _u64p)
 _sig("dds_pair_timing", C.c_int, C.c_void_p, _u64p, _u64p, _u64p, _u64p)
@@ -529,6 +534,32 @@ class Engine:
     def ope_order_device(self, d_col: int, d_valid: int | None, n: int, descending: bool, d_out: int):
         _check(_lib.dds_ope_order_device(self._h, C.c_void_p(d_col), C.c_void_p(d_valid or 0), n, int(descending),
                                          C.c_void_p(d_out)), "dds_ope_order_device")
+
+    def ope_rank(self, col, valid=None):
+        """dds_ope_rank: (labels, keys, counts) of the int64 keys `col` among the rows with valid[i] != 0 (None:
+        every row): labels[i] (uint32) = the dense rank of col[i] in ascending order, 0xFFFFFFFF for an invalid
+        row; keys (int64) = the distinct values; counts (uint64) = the rows holding each."""
+        col = np.ascontiguousarray(col, dtype=np.int64)
+        v = None if valid is None else np.ascontiguousarray(valid, dtype=np.uint8)
+        n = len(col)
+        labels = np.empty(max(1, n), dtype=np.uint32)
+        keys = np.empty(max(1, n), dtype=np.int64)
+        counts = np.empty(max(1, n), dtype=np.uint64)
+        ng = C.c_size_t()
+        _check(_lib.dds_ope_rank(self._h, col.ctypes.data, None if v is None else v.ctypes.data, n,
+                                 labels.ctypes.data_as(_u32p), keys.ctypes.data_as(_i64p),
+                                 counts.ctypes.data_as(_u64p), C.byref(ng)), "dds_ope_rank")
+        return labels[:n], keys[:ng.value].copy(), counts[:ng.value].copy()
+
+    def ope_rank_device(self, d_col: int, d_valid: int | None, n: int, d_labels: int | None, d_keys: int | None,
+                        d_counts: int | None) -> int:
+        """dds_ope_rank_device: the same on device pointers (uint32 labels and counts, int64 keys; any of the
+        three may be None); returns the number of distinct keys."""
+        ng = C.c_size_t()
+        _check(_lib.dds_ope_rank_device(self._h, C.c_void_p(d_col), C.c_void_p(d_valid or 0), n,
+                                        C.c_void_p(d_labels or 0), C.c_void_p(d_keys or 0),
+                                        C.c_void_p(d_counts or 0), C.byref(ng)), "dds_ope_rank_device")
+        return ng.value
 
     # ---- encryption ----
     def paillier_encrypt_batch(self, n: int, g: int, ms, rs) -> list[int]:
@@ -1007,6 +1038,48 @@ class Column(_Mutable):
                                         labels.ctypes.data_as(_u32p), ngroups, self._h,
                                         counts.ctypes.data_as(_u64p)), "dds_col_fold_groups")
         return counts[:ngroups]
+
+    @staticmethod
+    def _by_ope(by: "OpeColumn", mask, cap, call):
+        """call(mask pointer, mask words, keys, counts, cap, ngroups) -> status, with room for `cap` groups
+        (default: up to 4,096); a result with more groups is asked for again at the size the engine reports
+        (DDS_E_BUFSIZE wrote nothing). Returns (keys, counts) of the groups."""
+        words = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint64)
+        cap = max(1, min(len(by), 4096)) if cap is None else cap
+        ng = C.c_size_t()
+        while True:
+            keys, counts = np.empty(max(1, cap), dtype=np.int64), np.empty(max(1, cap), dtype=np.uint64)
+            rc = call(None if words is None else words.ctypes.data_as(_u64p), 0 if words is None else len(words),
+                      keys.ctypes.data_as(_i64p), counts.ctypes.data_as(_u64p), cap, C.byref(ng))
+            if rc != DDS_E_BUFSIZE or ng.value <= cap:
+                return rc, keys[:ng.value], counts[:ng.value]
+            cap = ng.value
+
+    def fold_by_ope(self, by: "OpeColumn", mask=None, cap: int | None = None):
+        """dds_col_fold_by_ope_be: SELECT key, SUM(x) GROUP BY key with the keys in the resident OPE column `by`
+        (row r of both columns is the same stored set). mask: uint64 row-mask words as OpeColumn.search_mask
+        returns them (a WHERE), or None. Returns (keys, values, counts): the distinct int64 keys of the
+        participating rows in ascending order, the product mod N of each key's rows as a canonical residue, and
+        how many rows that were."""
+        out = None
+
+        def call(m, mw, keys, counts, cap, ng):
+            nonlocal out
+            out = (C.c_uint8 * (self.mb * max(1, cap)))()
+            return _lib.dds_col_fold_by_ope_be(self._h, by._h, m, mw, out, keys, counts, cap, ng)
+
+        rc, keys, counts = self._by_ope(by, mask, cap, call)
+        _check(rc, "dds_col_fold_by_ope_be")
+        raw = C.string_at(C.addressof(out), self.mb * len(keys))
+        return keys, [int.from_bytes(raw[g * self.mb:(g + 1) * self.mb], "big") for g in range(len(keys))], counts
+
+    def append_fold_by_ope(self, src: "Column", by: "OpeColumn", mask=None, cap: int | None = None):
+        """dds_col_fold_by_ope: the same values of src's rows appended to this column, group g at the old
+        len(self) + g, canonical and live; returns (keys, counts)."""
+        rc, keys, counts = self._by_ope(by, mask, cap, lambda m, mw, keys, counts, cap, ng: _lib.dds_col_fold_by_ope(
+            src._h, by._h, m, mw, self._h, keys, counts, cap, ng))
+        _check(rc, "dds_col_fold_by_ope")
+        return keys, counts
 
     def fold_partial_device(self, d_partial: int, first: int = 0, count: int | None = None):
         """dds_col_fold_partial_device: the partial (partial_words u32) into device memory at d_partial."""

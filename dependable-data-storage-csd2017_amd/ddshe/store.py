@@ -415,6 +415,52 @@ class ResidentStore:
             raise ServerError(f"InvalidKeySpecException: {e}") from e
         return self._fold_by(self.by_pos_mult.get(position), by_position, n)
 
+    def _fold_by_ope(self, c: _CipherColumn | None, by_position: int, modulus: int, where) -> dict[int, str]:
+        """the grouped fold of column c keyed by the resident OPE column at by_position: the rows its resident
+        fold takes (500 / 404 as _fold_by) that hold an element at by_position and pass `where`, grouped by that
+        element's VALUE on the GPU (dds_col_fold_by_ope_be): no per-row host work, the mask is the only per-row
+        upload"""
+        if c is None or modulus != c.modulus:
+            raise ServerError("no resident column at this position under this modulus")
+        oc = self.ope.get(by_position)
+        if oc is None:
+            raise ServerError("no resident OPE column at the grouping position")
+        if c.bad:
+            raise ServerError("NumberFormatException: a qualifying element is not an integer")
+        if c.nlive == 0:
+            raise NotFound()
+        try:
+            mask = None
+            if where is not None:
+                route, position, value = where
+                wc = self.ope.get(position)
+                if wc is None:
+                    raise ServerError("no resident OPE column at the WHERE position")
+                mask, _ = wc.search_mask(_dec_text(value), routes._ROUTE_OP[route])
+            keys, vals, _ = c.col.fold_by_ope(oc, mask)
+        except DDSError as e:
+            raise ServerError(str(e)) from e
+        return {int(k): str(v) for k, v in zip(keys, vals)}
+
+    def sum_all_by_ope(self, position: int, by_position: int, nsqr: str, where=None) -> dict[int, str]:
+        """SELECT key, SUM(x) [WHERE ...] GROUP BY key: {value of the OPE element at by_position: Enc(sum of the
+        group's m) as decimal text} over the rows sum_all(position, nsqr) folds that hold an element at
+        by_position. where: (route, position, value) of a Search{Gt,GtEq,Lt,LtEq} on a resident OPE column,
+        whose row mask goes straight into the fold. Unlike sum_all_by, which groups by element text, "07" and "7"
+        are one group here. Raises ServerError when no OPE column is resident at by_position."""
+        x = _bigint(nsqr)
+        if x is None:
+            raise ServerError("NumberFormatException: nsqr")
+        return self._fold_by_ope(self.by_pos_sum.get(position), by_position, x, where)
+
+    def mult_all_by_ope(self, position: int, by_position: int, pubkey: str, where=None) -> dict[int, str]:
+        """MultAll per key, as sum_all_by_ope, under the modulus of pubkey."""
+        try:
+            n = rsa_modulus(pubkey)
+        except ValueError as e:
+            raise ServerError(f"InvalidKeySpecException: {e}") from e
+        return self._fold_by_ope(self.by_pos_mult.get(position), by_position, n, where)
+
     def search(self, route: str, position: int, value) -> list[str]:
         """POST /Search{Gt,GtEq,Lt,LtEq}?position (:682-830): matching keys in row order (the
         reference's order is unspecified). The match set comes back as a row bitmask."""

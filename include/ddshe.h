@@ -658,6 +658,46 @@ int dds_col_fold_groups_be(dds_col* col, const uint64_t* row_ids, size_t first, 
 int dds_fold_groups_plan(size_t n, size_t max_group, int* fan, int* levels, uint64_t* products,
                          uint64_t* workspace_rows);
 
+/* ---- GROUP BY an OPE column: dense ranks, and the grouped fold keyed by a resident dds_opecol ----------
+ * Dense ranks of int64 keys: *ngroups = the number of distinct values of col among the rows with valid[i] != 0
+ * (valid NULL: every row); labels[i] (nullable, n entries) = the rank of col[i] among them in ascending signed
+ * order, 0xFFFFFFFF for a row with valid[i] == 0; keys[g] (nullable, capacity n) = the g-th distinct value;
+ * counts[g] (nullable, capacity n) = the valid rows holding it. On the GPU: the stable radix sort of dds_ope_order,
+ * head flags where the sorted key changes, their scan tiled over workgroups, one scatter. The labels are what
+ * dds_col_fold_groups takes as `groups` with *ngroups groups (give it the valid rows only, or mark the others
+ * dead: 0xFFFFFFFF is no label). n == 0: DDS_OK with *ngroups = 0. A NULL ctx or ngroups, a NULL col with n > 0:
+ * DDS_E_ARG; n above 2^32 - 1: DDS_E_UNSUPPORTED; both before any GPU work. Thread-safe on one context. */
+int dds_ope_rank(dds_ctx*, const int64_t* col, const uint8_t* valid, size_t n, uint32_t* labels, int64_t* keys,
+                 uint64_t* counts, size_t* ngroups);
+/* The same on device-resident arrays (device pointers, d_labels / d_keys / d_counts nullable; 32-bit counts). */
+int dds_ope_rank_device(dds_ctx*, const int64_t* d_col, const uint8_t* d_valid, size_t n, uint32_t* d_labels,
+                        int64_t* d_keys, uint32_t* d_counts, size_t* ngroups);
+/* SELECT key, SUM(x) [WHERE ...] GROUP BY key over resident columns: row r of `col` and row r of `by` are the same
+ * stored set (dds_opecol_count(by) != dds_col_count(col), or columns of different contexts: DDS_E_ARG). Row r takes
+ * part iff it is live in col, live in by, holds the position in by (class != 0) and, when mask is not NULL, bit
+ * r % 64 of mask[r / 64] is set: the layout dds_opecol_search_mask writes, so a WHERE on any OPE column passes
+ * straight through (mask_words < ceil(count / 64): DDS_E_ARG). *ngroups = the distinct key values among the
+ * participating rows; group g is the g-th value in ascending order: keys[g], counts[g] >= 1 (both nullable, `cap`
+ * entries each) and the product mod N of its rows as a canonical residue, as dds_col_fold_groups gives it. No
+ * participating row: DDS_OK with *ngroups = 0. *ngroups > cap: DDS_E_BUFSIZE with *ngroups the count required,
+ * nothing written or appended. Elements compare by value ("07" and "7" are one group; a non-String element is
+ * fine). Decided from counts the key column keeps, before any GPU work: a live row of `by` that holds the position
+ * with a malformed element: DDS_E_FORMAT; with a decimal integer outside int64: DDS_E_UNSUPPORTED.
+ * Nothing per row crosses to the device but the optional mask: one kernel builds the sort's valid bytes, the sort
+ * and the rank kernels above label the rows, the group sizes come back in one copy, and the sorted permutation's
+ * valid tail is the segmented fold's id list (every group's rows in ascending row order). col and by are locked
+ * shared, out exclusively, all acquired together. Thread-safe on one context, no exception crosses; a workspace
+ * allocation that fails: DDS_E_NOMEM, nothing appended. With dds_ctx_set_timing on, the labelling (valid, sort,
+ * rank) adds to total_ms and the fold levels to fold_ms / launches / modmuls. */
+/* Column form: appends *ngroups canonical, live rows to out (same modulus and context, out != col, else DDS_E_ARG;
+ * capacity exceeded: DDS_E_ARG), group g at old count + g; nothing is published unless the whole call succeeds. */
+int dds_col_fold_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, dds_col* out,
+                        int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups);
+/* The same values as big-endian rows of the column's modulus width: out holds cap * mod_bytes bytes, *ngroups rows
+ * are written (out may be NULL when cap == 0). */
+int dds_col_fold_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, uint8_t* out,
+                           int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups);
+
 /* ---- device-resident batched encryption (BASELINE.json config 4) --------------
  * dds_col_fill_random: append `count` seeded random rows r < 2^bits (odd, so r != 0):
  *   limb l of row i = splitmix64(splitmix64(seed ^ (row0+i)) + l) in the column's rW layout.
