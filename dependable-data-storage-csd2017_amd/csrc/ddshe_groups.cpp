@@ -7,7 +7,9 @@
 // and neither uses nor touches the digit mirror.
 // Also here: the dense ranks of a key column (dds_ope_rank[_device], kernels in ddshe_rank.hip) and the grouped fold
 // keyed by a resident OPE column (dds_col_fold_by_ope[_be]), whose labels never leave the device: the stable sort's
-// permutation, cut where the key changes, is the same id list, and fold_segments runs the levels for both.
+// permutation, cut where the key changes, is the same id list, and fold_segments runs the levels for both. And the
+// cumulative SUM by key (dds_col_scan_by_ope[_be]): the same labelling and fold into a workspace, then one scan of
+// the group totals (scan_device of ddshe_scan.cpp).
 #include "ddshe_groups_plan.hpp"
 #include "ddshe_host.hpp"
 
@@ -311,7 +313,54 @@ void give_keys(const std::vector<int64_t>& k, const std::vector<uint32_t>& c, in
   give_counts(c, counts);
 }
 
+// the cumulative forms of give_keys' counts: the rows with key <= keys[g], or, suffix, with key >= keys[g]
+void give_running(const std::vector<int64_t>& k, const std::vector<uint32_t>& c, bool suffix, int64_t* keys,
+                  uint64_t* counts) {
+  if (keys) std::copy(k.begin(), k.end(), keys);
+  if (!counts) return;
+  uint64_t run = 0;
+  for (size_t i = 0; i < c.size(); ++i) {
+    const size_t g = suffix ? c.size() - 1 - i : i;
+    counts[g] = run += c[g];
+  }
+}
+
+// Cumulative SUM by key (dds_col_scan_by_ope[_be]): fold_by_ope_device leaves the group totals in w->x (canonical,
+// plain rows, stride *tstride; room(ng) may refuse first), then one scan of them, positional or reversed, into the
+// rows dest names. The caller holds the locks and has checked the arguments.
+template <class Room, class Dest>
+int scan_by_ope_device(dds_col* col, const OpeKeys& K, Worker* w, hipStream_t st, const uint64_t* mask, bool suffix,
+                       size_t cap, size_t* ngroups, std::vector<int64_t>* hkeys, std::vector<uint32_t>* hcounts,
+                       Room room, Dest dest) {
+  ModConsts& mc = *col->mc;
+  size_t tstride = 0;
+  auto totals = [&](size_t ng, uint32_t** O, size_t* ostride) {
+    int r = room(ng);
+    if (r) return r;
+    if ((r = check_rows(mc, ng))) return r;
+    tstride = round_up(ng, 64);
+    GRP_ALLOC(w->x.ensure((size_t)mc.S * tstride * 4));
+    *O = w->x.as<uint32_t>();
+    *ostride = tstride;
+    return (int)DDS_OK;
+  };
+  int rc;
+  if ((rc = fold_by_ope_device(col, K, w, st, mask, cap, ngroups, hkeys, hcounts, totals))) return rc;
+  const size_t ng = *ngroups;
+  if (ng == 0) return DDS_OK;
+  uint32_t* O = nullptr;
+  size_t ostride = 0;
+  if ((rc = dest(ng, tstride, &O, &ostride))) return rc;
+  return scan_device(col->ctx, w, st, mc, w->x.as<uint32_t>(), tstride, ng, nullptr, 0, ng, suffix, O, ostride);
+}
+
 }  // namespace
+
+namespace ddshe {
+namespace host {
+int scan_table(ModConsts& mc) { return groups_table(mc); }
+}  // namespace host
+}  // namespace ddshe
 
 extern "C" {
 
@@ -508,6 +557,86 @@ int dds_col_fold_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, s
     if (*ngroups == 0) return DDS_OK;
     if ((rc = rows_to_be(w, wl.st, mc, w->x.as<uint32_t>(), stride, *ngroups, false, out, mc.bytes))) return rc;
     give_keys(k, c, keys, counts);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_scan_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
+                        dds_col* out, int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups) {
+  try {
+    int rc = fold_by_ope_args(col, by, ngroups);
+    if (rc) return rc;
+    *ngroups = 0;
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    if (out == col) return fail(DDS_E_ARG, "out and the source column must differ");
+    ColWriteLock lk(out, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lr(col->mu, std::defer_lock);  // `col` and `by` are only read
+    std::shared_lock<std::shared_mutex> lb(opecol_mutex(by), std::defer_lock);
+    std::lock(lk.lk, lr, lb);
+    lk.touches_from(out->count);  // an append
+    if (col->ctx != out->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
+    if (bn::cmp(out->mc->N, col->mc->N) != 0 || out->mc->S != col->mc->S || out->mc->W != col->mc->W)
+      return fail(DDS_E_ARG, "columns must be over the same modulus");
+    const OpeKeys K = opecol_keys(by);
+    if ((rc = fold_by_ope_rows(col, K, mask, mask_words))) return rc;
+    if (K.count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    std::vector<int64_t> k;
+    std::vector<uint32_t> c;
+    auto room = [&](size_t ng) {
+      if (ng > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
+      return (int)DDS_OK;
+    };
+    // rows past the count: nothing is published unless the call succeeds
+    auto dest = [&](size_t, size_t, uint32_t** O, size_t* ostride) {
+      *O = out->d + out->count;
+      *ostride = out->stride;
+      return (int)DDS_OK;
+    };
+    if ((rc = scan_by_ope_device(col, K, wl.w, wl.st, mask, suffix != 0, cap, ngroups, &k, &c, room, dest))) return rc;
+    out->count += *ngroups;
+    give_running(k, c, suffix != 0, keys, counts);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_scan_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
+                           uint8_t* out, int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups) {
+  try {
+    int rc = fold_by_ope_args(col, by, ngroups);
+    if (rc) return rc;
+    *ngroups = 0;
+    if (cap && !out) return fail(DDS_E_ARG, "bad arguments");
+    std::shared_lock<std::shared_mutex> lr(col->mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lb(opecol_mutex(by), std::defer_lock);
+    std::lock(lr, lb);
+    ModConsts& mc = *col->mc;
+    const OpeKeys K = opecol_keys(by);
+    if ((rc = fold_by_ope_rows(col, K, mask, mask_words))) return rc;
+    if (K.count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    Worker* w = wl.w;
+    std::vector<int64_t> k;
+    std::vector<uint32_t> c;
+    size_t stride = 0;
+    auto room = [](size_t) { return (int)DDS_OK; };
+    auto dest = [&](size_t, size_t tstride, uint32_t** O, size_t* ostride) {
+      stride = tstride;
+      GRP_ALLOC(w->x2.ensure((size_t)mc.S * stride * 4));
+      *O = w->x2.as<uint32_t>();
+      *ostride = stride;
+      return (int)DDS_OK;
+    };
+    if ((rc = scan_by_ope_device(col, K, w, wl.st, mask, suffix != 0, cap, ngroups, &k, &c, room, dest))) return rc;
+    if (*ngroups == 0) return DDS_OK;
+    if ((rc = rows_to_be(w, wl.st, mc, w->x2.as<uint32_t>(), stride, *ngroups, false, out, mc.bytes))) return rc;
+    give_running(k, c, suffix != 0, keys, counts);
     return DDS_OK;
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");

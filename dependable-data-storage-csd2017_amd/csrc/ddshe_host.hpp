@@ -1,5 +1,6 @@
 // Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp, ddshe_opecol.cpp,
-// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp, ddshe_groups.cpp):
+// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp, ddshe_groups.cpp,
+// ddshe_scan.cpp):
 // contexts, stream/buffer pools, per-modulus Montgomery constants, device columns and the
 // orchestration helpers around the HIP kernels. Not part of the public ABI (include/ddshe.h).
 #pragma once
@@ -113,6 +114,8 @@ struct Worker {
   // dense ranks (ddshe_rank.hip): the sorted permutation, the tiles' head counts, the segment starts, the distinct
   // keys, the labels, and for dds_col_fold_by_ope the valid bytes and the caller's row mask
   DevBuf rk_perm, rk_sums, rk_start, rk_keys, rk_lab, rk_valid, rk_mask;
+  // running totals (ddshe_scan.cpp): the upper levels' planes (totals, carries), the call's row ids
+  DevBuf scan_lv, scan_ids;
   DevBuf crt[7];  // CRT scratch of Paillier encryption and decryption (encrypt_crt_device, decrypt_crt_device)
   hipEvent_t ev[4] = {};
   // decimal codec: double-buffered pinned chunks (chars, offsets), their device copies,
@@ -643,6 +646,16 @@ int exprows_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const
 // written. Synchronises the stream. With the context's timing on, the kernels' device time goes to total_ms.
 int inv_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* d_x, size_t xstride,
                const uint32_t* d_num, size_t nstride, size_t count, uint32_t* d_out, size_t ostride, size_t* bad_row);
+// Running totals on the device (ddshe_scan.cpp, ddshe_scan_plan.hpp): row j of O <- x_0 · … · x_j mod N, canonical,
+// over the call's n >= 1 rows of X (xrows rows at xstride, below 2N): x_j = row d_list[j] (a device list of n ids,
+// each below xrows), or row first + j when d_list is null. suffix: row j of O <- x_j · … · x_(n-1); with a list the
+// caller passes it reversed (d_list[j] = the id of input n - 1 - j). O (n rows at ostride) must not overlap X.
+// Synchronises the stream. With the context's timing on, the launches add to fold_ms and fold_launches and the
+// plan's products to fold_modmuls. A workspace allocation that fails: DDS_E_NOMEM.
+int scan_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride, size_t xrows,
+                const uint32_t* d_list, size_t first, size_t n, bool suffix, uint32_t* O, size_t ostride);
+// the modulus' table R^k mod N, k = 0 .. F + 1 (mc.dgtab), built on first use (ddshe_groups.cpp)
+int scan_table(ModConsts& mc);
 int product_tree(dds_ctx* ctx, const std::vector<uint32_t>& h, size_t count, size_t len, size_t cap16, bn::Limbs* out);
 int fold_even_modulus(dds_ctx* ctx, const bn::Limbs& M, const std::vector<bn::Limbs>& xs, const std::vector<bool>& negs,
                       bn::Limbs* out);

@@ -201,6 +201,25 @@ hipError_t launch_grp_fold(int S, bool idx, const uint32_t* X, size_t xstride, s
                            size_t cap, const void* desc, size_t nchunks, const uint32_t* consts, uint32_t n0,
                            const uint32_t* tab, uint32_t* B, size_t bstride, size_t brows, uint32_t* O, size_t ostride,
                            size_t orows, hipStream_t st);
+// Running totals (ddshe_scan.hip, ddshe_scan_plan.hpp), one launch per level and direction. The call's j-th row,
+// j < n <= 2^32 - 1, is row list[j] of X (list given), first + j, or first + n - 1 - j (rev_in); xrows rows of X may
+// be read. launch_scan_up_rows: the totals of level 0's chunks, prod·R, to rows [0, nchunks) of T.
+// launch_scan_up: the same over the `count` rows of Tin (an upper level). launch_scan_carry: C[row] = the carry
+// into row `row` of a level of `count` rows whose totals are T (both at `stride`), chunk c starting from row c of
+// Cin, or, Cin null, the level's only chunk from R mod N. launch_scan_down_rows: the running totals themselves,
+// canonical, row j to row j of O, or n - 1 - j (rev_out); orows >= n rows of O may be written; Cin null: n <= the
+// fan and the carry is R mod N. tab as launch_grp_fold's.
+hipError_t launch_scan_up_rows(int S, const uint32_t* X, size_t xstride, size_t xrows, const uint32_t* list,
+                               uint32_t first, bool rev_in, size_t n, const uint32_t* consts, uint32_t n0,
+                               const uint32_t* tab, uint32_t* T, size_t tstride, hipStream_t st);
+hipError_t launch_scan_up(int S, const uint32_t* Tin, size_t istride, size_t count, const uint32_t* consts,
+                          uint32_t n0, uint32_t* Tout, size_t ostride, hipStream_t st);
+hipError_t launch_scan_carry(int S, const uint32_t* T, uint32_t* C, size_t stride, size_t count,
+                             const uint32_t* consts, uint32_t n0, const uint32_t* Cin, size_t cstride, hipStream_t st);
+hipError_t launch_scan_down_rows(int S, const uint32_t* X, size_t xstride, size_t xrows, const uint32_t* list,
+                                 uint32_t first, bool rev_in, size_t n, const uint32_t* consts, uint32_t n0,
+                                 const uint32_t* tab, const uint32_t* Cin, size_t cstride, uint32_t* O, size_t ostride,
+                                 size_t orows, bool rev_out, hipStream_t st);
 // Prime search (ddshe_prime.hpp). launch_strong1: lane t < nlanes tests row idx[t / rounds] (t / rounds when idx is
 // null) of Ncol (S1 = 20 | 40 | 56 limbs of 28 bits, odd, >= 3, at most nbits <= 28 S1 - 2 bits each) to base 2
 // (base2), to row t of Bcol, or with Bcol null to the witness of (seed, row, t % rounds), N >= 5; out[t] = 1 iff

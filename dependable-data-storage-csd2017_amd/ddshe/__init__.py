@@ -74,6 +74,7 @@ EXPORTS = [
     "dds_modinv_rows", "dds_col_append_inv", "dds_col_append_quot", "dds_col_append_mul",
     "dds_col_fold_groups", "dds_col_fold_groups_be", "dds_fold_groups_plan",
     "dds_ope_rank", "dds_ope_rank_device", "dds_col_fold_by_ope", "dds_col_fold_by_ope_be",
+    "dds_col_append_scan", "dds_col_scan_be", "dds_scan_plan", "dds_col_scan_by_ope", "dds_col_scan_by_ope_be",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -194,6 +195,11 @@ _sig("dds_ope_rank", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _u32p, _i
 _sig("dds_ope_rank_device", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _szp)
 _sig("dds_col_fold_by_ope", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_void_p, _i64p, _u64p, _sz, _szp)
 _sig("dds_col_fold_by_ope_be", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, _u8p, _i64p, _u64p, _sz, _szp)
+_sig("dds_col_append_scan", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, _sz, C.c_int)
+_sig("dds_col_scan_be", C.c_int, C.c_void_p, _u64p, _sz, _sz, C.c_int, _u8p)
+_sig("dds_scan_plan", C.c_int, _sz, C.POINTER(C.c_int), C.POINTER(C.c_int), _u64p, _u64p)
+_sig("dds_col_scan_by_ope", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_int, C.c_void_p, _i64p, _u64p, _sz, _szp)
+_sig("dds_col_scan_by_ope_be", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_int, _u8p, _i64p, _u64p, _sz, _szp)
 _sig("dds_pair_modmul_dec", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _sz, _szp)
 _sig("dds_pair_stats", C.c_int, C.c_void_p, _u64p, _u64p)
 _sig("dds_pair_timing", C.c_int, C.c_void_p, _u64p, _u64p, _u64p, _u64p)
@@ -765,6 +771,13 @@ class Engine:
                "dds_fold_groups_plan")
         return f.value, lv.value, pr.value, ws.value
 
+    @staticmethod
+    def scan_plan(n: int) -> tuple:
+        """dds_scan_plan: (fan, levels, products, workspace rows) of the running totals of n rows. No GPU work."""
+        f, lv, pr, ws = C.c_int(), C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(_lib.dds_scan_plan(n, C.byref(f), C.byref(lv), C.byref(pr), C.byref(ws)), "dds_scan_plan")
+        return f.value, lv.value, pr.value, ws.value
+
     def host_register(self, arr: np.ndarray):
         """dds_host_register: page-lock a reusable output array (results DMA'd straight into it)."""
         _check(_lib.dds_host_register(self._h, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "dds_host_register")
@@ -1079,6 +1092,55 @@ class Column(_Mutable):
         rc, keys, counts = self._by_ope(by, mask, cap, lambda m, mw, keys, counts, cap, ng: _lib.dds_col_fold_by_ope(
             src._h, by._h, m, mw, self._h, keys, counts, cap, ng))
         _check(rc, "dds_col_fold_by_ope")
+        return keys, counts
+
+    def _scan_args(self, row_ids, first, count):
+        if row_ids is None:
+            return None, len(self) - first if count is None else count
+        ids = np.ascontiguousarray(row_ids, dtype=np.uint64)
+        return ids, len(ids)
+
+    def append_scan(self, src: "Column", row_ids=None, first: int = 0, count: int | None = None,
+                    suffix: bool = False):
+        """dds_col_append_scan: append the running totals of src's rows row_ids (or [first, first+count)), taken in
+        order: row j = x_0 * ... * x_j mod N (Enc(m_0 + ... + m_j) for a Paillier column), with suffix
+        x_j * ... * x_(n-1); canonical and live, row j at the old len(self) + j. Positional: liveness is ignored."""
+        ids, n = src._scan_args(row_ids, first, count)
+        _check(_lib.dds_col_append_scan(self._h, src._h, None if ids is None else ids.ctypes.data_as(_u64p), first, n,
+                                        int(bool(suffix))), "dds_col_append_scan")
+
+    def scan(self, row_ids=None, first: int = 0, count: int | None = None, suffix: bool = False) -> list:
+        """dds_col_scan_be: the same running totals as a list of canonical residues."""
+        ids, n = self._scan_args(row_ids, first, count)
+        out = (C.c_uint8 * (self.mb * max(1, n)))()
+        _check(_lib.dds_col_scan_be(self._h, None if ids is None else ids.ctypes.data_as(_u64p), first, n,
+                                    int(bool(suffix)), out), "dds_col_scan_be")
+        raw = C.string_at(C.addressof(out), self.mb * n)
+        return [int.from_bytes(raw[j * self.mb:(j + 1) * self.mb], "big") for j in range(n)]
+
+    def scan_by_ope(self, by: "OpeColumn", mask=None, cap: int | None = None, suffix: bool = False):
+        """dds_col_scan_by_ope_be: SELECT key, SUM(x) OVER (ORDER BY key) with the keys in the resident OPE column
+        `by`; participation and mask as fold_by_ope. Returns (keys, values, counts): the distinct keys in
+        ascending order, for each the product mod N of the participating rows with key <= it (suffix: >= it) as
+        a canonical residue, and how many rows that were."""
+        out = None
+
+        def call(m, mw, keys, counts, cap, ng):
+            nonlocal out
+            out = (C.c_uint8 * (self.mb * max(1, cap)))()
+            return _lib.dds_col_scan_by_ope_be(self._h, by._h, m, mw, int(bool(suffix)), out, keys, counts, cap, ng)
+
+        rc, keys, counts = self._by_ope(by, mask, cap, call)
+        _check(rc, "dds_col_scan_by_ope_be")
+        raw = C.string_at(C.addressof(out), self.mb * len(keys))
+        return keys, [int.from_bytes(raw[g * self.mb:(g + 1) * self.mb], "big") for g in range(len(keys))], counts
+
+    def append_scan_by_ope(self, col: "Column", by: "OpeColumn", mask=None, suffix: bool = False):
+        """dds_col_scan_by_ope: the same cumulative values of col's rows appended to this column, key g at the old
+        len(self) + g, canonical and live; returns (keys, counts)."""
+        rc, keys, counts = self._by_ope(by, mask, None, lambda m, mw, keys, counts, cap, ng: _lib.dds_col_scan_by_ope(
+            col._h, by._h, m, mw, int(bool(suffix)), self._h, keys, counts, cap, ng))
+        _check(rc, "dds_col_scan_by_ope")
         return keys, counts
 
     def fold_partial_device(self, d_partial: int, first: int = 0, count: int | None = None):

@@ -415,11 +415,13 @@ class ResidentStore:
             raise ServerError(f"InvalidKeySpecException: {e}") from e
         return self._fold_by(self.by_pos_mult.get(position), by_position, n)
 
-    def _fold_by_ope(self, c: _CipherColumn | None, by_position: int, modulus: int, where) -> dict[int, str]:
+    def _fold_by_ope(self, c: _CipherColumn | None, by_position: int, modulus: int, where,
+                     descending: bool | None = None) -> dict[int, str]:
         """the grouped fold of column c keyed by the resident OPE column at by_position: the rows its resident
         fold takes (500 / 404 as _fold_by) that hold an element at by_position and pass `where`, grouped by that
         element's VALUE on the GPU (dds_col_fold_by_ope_be): no per-row host work, the mask is the only per-row
-        upload"""
+        upload. descending (not None): the cumulative values instead (dds_col_scan_by_ope_be): over the keys up to
+        each key (False), or from each key on (True)"""
         if c is None or modulus != c.modulus:
             raise ServerError("no resident column at this position under this modulus")
         oc = self.ope.get(by_position)
@@ -437,7 +439,10 @@ class ResidentStore:
                 if wc is None:
                     raise ServerError("no resident OPE column at the WHERE position")
                 mask, _ = wc.search_mask(_dec_text(value), routes._ROUTE_OP[route])
-            keys, vals, _ = c.col.fold_by_ope(oc, mask)
+            if descending is None:
+                keys, vals, _ = c.col.fold_by_ope(oc, mask)
+            else:
+                keys, vals, _ = c.col.scan_by_ope(oc, mask, suffix=descending)
         except DDSError as e:
             raise ServerError(str(e)) from e
         return {int(k): str(v) for k, v in zip(keys, vals)}
@@ -460,6 +465,26 @@ class ResidentStore:
         except ValueError as e:
             raise ServerError(f"InvalidKeySpecException: {e}") from e
         return self._fold_by_ope(self.by_pos_mult.get(position), by_position, n, where)
+
+    def running_sum_by_ope(self, position: int, by_position: int, nsqr: str, where=None,
+                           descending: bool = False) -> dict[int, str]:
+        """SELECT key, SUM(x) OVER (ORDER BY key) [WHERE ...]: {value of the OPE element at by_position:
+        Enc(sum of m over the rows whose key is <= it) as decimal text}, over the rows sum_all_by_ope groups and
+        with its `where`. descending: the rows whose key is >= it (ORDER BY key DESC). One labelling, one
+        segmented fold and one scan of the key totals on the GPU (dds_col_scan_by_ope_be)."""
+        x = _bigint(nsqr)
+        if x is None:
+            raise ServerError("NumberFormatException: nsqr")
+        return self._fold_by_ope(self.by_pos_sum.get(position), by_position, x, where, descending=bool(descending))
+
+    def running_mult_by_ope(self, position: int, by_position: int, pubkey: str, where=None,
+                            descending: bool = False) -> dict[int, str]:
+        """The running MultAll by key, as running_sum_by_ope, under the modulus of pubkey."""
+        try:
+            n = rsa_modulus(pubkey)
+        except ValueError as e:
+            raise ServerError(f"InvalidKeySpecException: {e}") from e
+        return self._fold_by_ope(self.by_pos_mult.get(position), by_position, n, where, descending=bool(descending))
 
     def search(self, route: str, position: int, value) -> list[str]:
         """POST /Search{Gt,GtEq,Lt,LtEq}?position (:682-830): matching keys in row order (the

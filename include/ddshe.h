@@ -698,6 +698,49 @@ int dds_col_fold_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size
 int dds_col_fold_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, uint8_t* out,
                            int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups);
 
+/* ---- running totals: prefix products of resident rows ----------
+ * The scan beside the folds (reductions) and the row-wise calls (maps): out row j = x_0 * ... * x_j mod N over the
+ * call's rows taken in order, Enc(m_0 + ... + m_j) for a Paillier column, the running product for an RSA one; with
+ * suffix != 0, out row j = x_j * ... * x_(n-1). out row j always belongs to input j. The rows are cut into
+ * contiguous chunks of 32, one lane group each: chunk totals upward level by level until at most 32 remain, their
+ * exclusive carries in one lane group, the carries back down, and at the rows one product for the chain and one
+ * with a constant per total, about 3 products per row. Every level and direction is a launch of its own (no kernel
+ * waits on another workgroup) and the device does all of it: 2 * levels + 1 launches, one synchronisation.
+ * Any odd modulus of the lane-group shapes; the opaque rows only (the digit mirror is neither used nor touched).
+ * Rows are row_ids[0..n), or [first, first+n) when row_ids is NULL. Positional like dds_col_append_quot: liveness
+ * is ignored, the id list says which rows take part (dds_opecol_order lists live holders only), a row id listed
+ * twice contributes twice. Every output is the canonical residue in [0, N), row 0 included; a zero row makes every
+ * later total 0 (no units are needed).
+ * All checks run before any GPU work, and on any error nothing is written or appended. DDS_E_ARG: a NULL handle or
+ * out, out == in, columns over different moduli or contexts, rows past the end, a row id out of range
+ * (dds_last_error names its index), out's capacity exceeded. n above 2^32 - 1: DDS_E_UNSUPPORTED. n == 0: DDS_OK,
+ * nothing is read or appended. A workspace allocation that fails: DDS_E_NOMEM, nothing appended. Thread-safe on one
+ * context, on a stream of its pool, no exception crosses. With dds_ctx_set_timing on, the scan's launches add to
+ * fold_ms and launches, and exactly dds_scan_plan's products to dds_ctx_get_fold_work's modmuls. */
+/* Column form: appends n canonical, live rows to out, row j at old count + j, published only if the whole call
+ * succeeds. out is locked exclusively, in shared, both acquired together. */
+int dds_col_append_scan(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n, int suffix);
+/* The same values as big-endian rows of the column's modulus width: out holds n * mod_bytes bytes. */
+int dds_col_scan_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, int suffix, uint8_t* out);
+/* What a scan of n rows does: the fan (rows per lane group and level), the levels of chunk totals above the rows
+ * (0 up to 32 rows; a call of n >= 1 rows is 2 * levels + 1 launches), the Montgomery products (2n - 1 up to 32
+ * rows; above, with c_i the rows of level i: n + (2n - c_1) at the rows, 2 (c_i - c_(i+1)) per level between, and
+ * c_top - 1 at the top) and the scratch rows beyond out. n == 0: levels 0, products 0. n above 2^32 - 1:
+ * DDS_E_UNSUPPORTED. Every output is nullable. No GPU work. */
+int dds_scan_plan(size_t n, int* fan, int* levels, uint64_t* products, uint64_t* workspace_rows);
+/* Cumulative SUM by key over resident columns (SELECT key, SUM(x) OVER (ORDER BY key)): participation, keys[g],
+ * errors and locking exactly as dds_col_fold_by_ope; the value of group g is the product of the participating rows
+ * with key <= keys[g] (suffix != 0: key >= keys[g]), canonical, and counts[g] the number of those rows
+ * (cumulative, summed on the host from the group sizes). The labelling and the segmented fold of
+ * dds_col_fold_by_ope leave the *ngroups group totals on the device, and one scan of them (positional, reversed
+ * for suffix) gives the values. *ngroups > cap: DDS_E_BUFSIZE with *ngroups the count required, nothing written or
+ * appended. No participating row: DDS_OK with *ngroups = 0. Timing: the labelling adds to total_ms, the fold
+ * levels and the scan to fold_ms / launches / modmuls. */
+int dds_col_scan_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
+                        dds_col* out, int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups);
+int dds_col_scan_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
+                           uint8_t* out, int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups);
+
 /* ---- device-resident batched encryption (BASELINE.json config 4) --------------
  * dds_col_fill_random: append `count` seeded random rows r < 2^bits (odd, so r != 0):
  *   limb l of row i = splitmix64(splitmix64(seed ^ (row0+i)) + l) in the column's rW layout.
