@@ -9,9 +9,12 @@
 // keyed by a resident OPE column (dds_col_fold_by_ope[_be]), whose labels never leave the device: the stable sort's
 // permutation, cut where the key changes, is the same id list, and fold_segments runs the levels for both. And the
 // cumulative SUM by key (dds_col_scan_by_ope[_be]): the same labelling and fold into a workspace, then one scan of
-// the group totals (scan_device of ddshe_scan.cpp).
+// the group totals (scan_device of ddshe_scan.cpp). And the running totals inside each key
+// (dds_col_scan_part_by_ope[_be]): the same labelling, then one segmented scan over the sorted permutation
+// (seg_scan_device of ddshe_scan.cpp).
 #include "ddshe_groups_plan.hpp"
 #include "ddshe_host.hpp"
+#include "ddshe_scan_plan.hpp"
 
 using namespace ddshe;
 using namespace ddshe::host;
@@ -228,15 +231,12 @@ int rank_args(dds_ctx* ctx, const void* col, size_t n, size_t* ngroups) {
   return DDS_OK;
 }
 
-// The grouped fold of `col` keyed by the resident OPE column K (dds_col_fold_by_ope[_be]); the caller holds both
-// columns' locks and has checked the arguments. The valid kernel, the sort and the rank kernels label the rows on the
-// device; the sorted permutation's valid tail is the segmented fold's id list as it stands. *ngroups <- the
-// distinct keys among the participating rows; above cap: DDS_E_BUFSIZE before anything is written. dest(ngroups, &O,
-// &ostride) then names the rows the values go to (or fails). hkeys / hcounts: filled on success only.
-template <class Dest>
-int fold_by_ope_device(dds_col* col, const OpeKeys& K, Worker* w, hipStream_t st, const uint64_t* mask, size_t cap,
-                       size_t* ngroups, std::vector<int64_t>* hkeys, std::vector<uint32_t>* hcounts, Dest dest) {
-  dds_ctx* ctx = col->ctx;
+// The labelling every call keyed by a resident OPE column starts with: the optional mask goes up, the valid kernel,
+// the sort and the rank kernels run; *ng <- the distinct keys among the participating rows (one small read-back),
+// their sizes are enqueued into *d_cnt, the keys lie in w->rk_keys, the permutation in w->rk_perm, the segment starts
+// in w->rk_start. timed: w->ev[2] and w->ev[3] bracket it.
+int label_by_ope(dds_col* col, const OpeKeys& K, Worker* w, hipStream_t st, const uint64_t* mask, bool timed, size_t* ng,
+                 const uint32_t** d_cnt) {
   const size_t n = K.count, words = (n + 63) / 64;
   int rc;
   if ((rc = groups_table(*col->mc))) return rc;
@@ -248,16 +248,31 @@ int fold_by_ope_device(dds_col* col, const OpeKeys& K, Worker* w, hipStream_t st
     HIP_TRY(hipMemcpyAsync(w->rk_mask.p, mask, words * 8, hipMemcpyHostToDevice, st));  // one bit per row
     d_mask = w->rk_mask.as<uint64_t>();
   }
-  const bool timed = ctx->timing.load();
   if (timed) HIP_TRY(hipEventRecord(w->ev[2], st));
   HIP_TRY(launch_by_valid(K.d_cls, K.hold, K.d_dead, col->ndead ? col->dlive : nullptr, d_mask, n,
                           w->rk_valid.as<uint8_t>(), st));
-  size_t ng = 0;
-  const uint32_t* d_cnt = nullptr;
   if ((rc = rank_device(w, st, K.d_val, w->rk_valid.as<uint8_t>(), n, K.ubounds, nullptr, w->rk_keys.as<int64_t>(),
-                        true, nullptr, &ng, &d_cnt)))
+                        true, nullptr, ng, d_cnt)))
     return rc;
   if (timed) HIP_TRY(hipEventRecord(w->ev[3], st));
+  return DDS_OK;
+}
+
+// The grouped fold of `col` keyed by the resident OPE column K (dds_col_fold_by_ope[_be]); the caller holds both
+// columns' locks and has checked the arguments. The valid kernel, the sort and the rank kernels label the rows on the
+// device; the sorted permutation's valid tail is the segmented fold's id list as it stands. *ngroups <- the
+// distinct keys among the participating rows; above cap: DDS_E_BUFSIZE before anything is written. dest(ngroups, &O,
+// &ostride) then names the rows the values go to (or fails). hkeys / hcounts: filled on success only.
+template <class Dest>
+int fold_by_ope_device(dds_col* col, const OpeKeys& K, Worker* w, hipStream_t st, const uint64_t* mask, size_t cap,
+                       size_t* ngroups, std::vector<int64_t>* hkeys, std::vector<uint32_t>* hcounts, Dest dest) {
+  dds_ctx* ctx = col->ctx;
+  const size_t n = K.count;
+  const bool timed = ctx->timing.load();
+  int rc;
+  size_t ng = 0;
+  const uint32_t* d_cnt = nullptr;
+  if ((rc = label_by_ope(col, K, w, st, mask, timed, &ng, &d_cnt))) return rc;
   *ngroups = ng;
   if (ng > cap) {
     HIP_TRY(hipStreamSynchronize(st));  // the counts kernel is done with the worker's buffers
@@ -352,6 +367,83 @@ int scan_by_ope_device(dds_col* col, const OpeKeys& K, Worker* w, hipStream_t st
   size_t ostride = 0;
   if ((rc = dest(ng, tstride, &O, &ostride))) return rc;
   return scan_device(col->ctx, w, st, mc, w->x.as<uint32_t>(), tstride, ng, nullptr, 0, ng, suffix, O, ostride);
+}
+
+// Running totals inside each key (dds_col_scan_part_by_ope[_be]): fold_by_ope_device's labelling, then one segmented
+// scan over the sorted permutation's valid tail as it stands (read backwards for a suffix scan), its head bytes made
+// on the device from w->rk_start. Slot t of the output is the t-th participating row in (key, row id) order. The
+// keys, the sizes and the permutation come back in one copy; *nrows, *ngroups <- what the call needs, above either
+// cap: DDS_E_BUFSIZE before anything is written. dest(nrows, &O, &ostride) names the rows the values go to (or
+// fails). hkeys / hcounts / hrows: filled on success only. The caller holds the locks and has checked the arguments.
+template <class Dest>
+int scan_part_by_ope_device(dds_col* col, const OpeKeys& K, Worker* w, hipStream_t st, const uint64_t* mask, bool suffix,
+                            size_t cap_rows, size_t cap_groups, size_t* nrows, size_t* ngroups,
+                            std::vector<int64_t>* hkeys, std::vector<uint32_t>* hcounts, std::vector<uint32_t>* hrows,
+                            Dest dest) {
+  dds_ctx* ctx = col->ctx;
+  const size_t n = K.count;
+  const bool timed = ctx->timing.load();
+  int rc;
+  size_t ng = 0;
+  const uint32_t* d_cnt = nullptr;
+  if ((rc = label_by_ope(col, K, w, st, mask, timed, &ng, &d_cnt))) return rc;
+  *ngroups = ng;
+  if (ng == 0) {
+    HIP_TRY(hipStreamSynchronize(st));
+    return DDS_OK;
+  }
+  // keys, sizes and the permutation through the pinned read-back buffer, one after the other
+  GRP_ALLOC(w->hbig.ensure(ng * 12 + n * 4));
+  int64_t* pk = (int64_t*)w->hbig.p;
+  uint32_t* pc = (uint32_t*)(pk + ng);
+  uint32_t* pr = pc + ng;
+  HIP_TRY(hipMemcpyAsync(pk, w->rk_keys.p, ng * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(pc, d_cnt, ng * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(pr, w->rk_perm.p, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float label_ms = 0;  // read now: the scan records the same events for its flags
+  if (timed) HIP_TRY(hipEventElapsedTime(&label_ms, w->ev[2], w->ev[3]));
+  size_t nvalid = 0;
+  for (size_t g = 0; g < ng; ++g) nvalid += pc[g];
+  if (nvalid > n || nvalid < ng) return fail(DDS_E_HIP, "group sizes do not fit the column's rows");
+  *nrows = nvalid;
+  if (ng > cap_groups || nvalid > cap_rows)
+    return fail(DDS_E_BUFSIZE, std::to_string(nvalid) + " rows in " + std::to_string(ng) + " groups, room for " +
+                                   std::to_string(cap_rows) + " and " + std::to_string(cap_groups));
+  hkeys->assign(pk, pk + ng);
+  hcounts->assign(pc, pc + ng);
+  // the invalid rows come first in the permutation: the participating ones are its last nvalid slots
+  const size_t base = n - nvalid;
+  hrows->assign(pr + base, pr + n);
+  std::vector<size_t> starts(ng);
+  for (size_t g = 0, at = 0; g < ng; at += pc[g++]) {
+    if (pc[g] == 0) return fail(DDS_E_HIP, "an empty group among the ranks");
+    starts[g] = at;
+  }
+  uint32_t* O = nullptr;
+  size_t ostride = 0;
+  if ((rc = dest(nvalid, &O, &ostride))) return rc;
+  if ((rc = seg_scan_device(ctx, w, st, *col->mc, col->d, col->stride, col->count, w->rk_perm.as<uint32_t>() + base,
+                            true, 0, nvalid, suffix, seg_heads(nvalid, starts.data(), ng, suffix),
+                            w->rk_start.as<uint32_t>(), ng, (uint32_t)base, O, ostride)))
+    return rc;
+  if (timed) {
+    std::lock_guard<std::mutex> lk(ctx->tmu);
+    ctx->total_ms += label_ms;
+  }
+  return DDS_OK;
+}
+
+void give_rows(const std::vector<uint32_t>& r, uint64_t* rows) {
+  if (rows)
+    for (size_t t = 0; t < r.size(); ++t) rows[t] = r[t];
+}
+
+int scan_part_args(const dds_col* col, const dds_opecol* by, size_t* nrows, size_t* ngroups) {
+  if (!col || !by || !nrows || !ngroups) return fail(DDS_E_ARG, "bad arguments");
+  *nrows = 0;
+  *ngroups = 0;
+  return DDS_OK;
 }
 
 }  // namespace
@@ -637,6 +729,90 @@ int dds_col_scan_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, s
     if (*ngroups == 0) return DDS_OK;
     if ((rc = rows_to_be(w, wl.st, mc, w->x2.as<uint32_t>(), stride, *ngroups, false, out, mc.bytes))) return rc;
     give_running(k, c, suffix != 0, keys, counts);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_scan_part_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
+                             dds_col* out, uint64_t* rows, size_t cap_rows, int64_t* keys, uint64_t* counts,
+                             size_t cap_groups, size_t* nrows, size_t* ngroups) {
+  try {
+    int rc = scan_part_args(col, by, nrows, ngroups);
+    if (rc) return rc;
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    if (out == col) return fail(DDS_E_ARG, "out and the source column must differ");
+    ColWriteLock lk(out, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lr(col->mu, std::defer_lock);  // `col` and `by` are only read
+    std::shared_lock<std::shared_mutex> lb(opecol_mutex(by), std::defer_lock);
+    std::lock(lk.lk, lr, lb);
+    lk.touches_from(out->count);  // an append
+    if (col->ctx != out->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
+    if (bn::cmp(out->mc->N, col->mc->N) != 0 || out->mc->S != col->mc->S || out->mc->W != col->mc->W)
+      return fail(DDS_E_ARG, "columns must be over the same modulus");
+    const OpeKeys K = opecol_keys(by);
+    if ((rc = fold_by_ope_rows(col, K, mask, mask_words))) return rc;
+    if (K.count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    std::vector<int64_t> k;
+    std::vector<uint32_t> c, r;
+    // rows past the count: nothing is published unless the call succeeds
+    auto dest = [&](size_t nr, uint32_t** O, size_t* ostride) {
+      if (nr > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
+      *O = out->d + out->count;
+      *ostride = out->stride;
+      return (int)DDS_OK;
+    };
+    if ((rc = scan_part_by_ope_device(col, K, wl.w, wl.st, mask, suffix != 0, cap_rows, cap_groups, nrows, ngroups, &k,
+                                      &c, &r, dest)))
+      return rc;
+    out->count += *nrows;
+    give_keys(k, c, keys, counts);
+    give_rows(r, rows);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_scan_part_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
+                                uint8_t* out, uint64_t* rows, size_t cap_rows, int64_t* keys, uint64_t* counts,
+                                size_t cap_groups, size_t* nrows, size_t* ngroups) {
+  try {
+    int rc = scan_part_args(col, by, nrows, ngroups);
+    if (rc) return rc;
+    if (cap_rows && !out) return fail(DDS_E_ARG, "bad arguments");
+    std::shared_lock<std::shared_mutex> lr(col->mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lb(opecol_mutex(by), std::defer_lock);
+    std::lock(lr, lb);
+    ModConsts& mc = *col->mc;
+    const OpeKeys K = opecol_keys(by);
+    if ((rc = fold_by_ope_rows(col, K, mask, mask_words))) return rc;
+    if (K.count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    Worker* w = wl.w;
+    std::vector<int64_t> k;
+    std::vector<uint32_t> c, r;
+    size_t stride = 0;
+    auto dest = [&](size_t nr, uint32_t** O, size_t* ostride) {
+      int e = check_rows(mc, nr);
+      if (e) return e;
+      stride = round_up(nr, 64);
+      GRP_ALLOC(w->x.ensure((size_t)mc.S * stride * 4));
+      *O = w->x.as<uint32_t>();
+      *ostride = stride;
+      return (int)DDS_OK;
+    };
+    if ((rc = scan_part_by_ope_device(col, K, w, wl.st, mask, suffix != 0, cap_rows, cap_groups, nrows, ngroups, &k, &c,
+                                      &r, dest)))
+      return rc;
+    if (*nrows == 0) return DDS_OK;
+    if ((rc = rows_to_be(w, wl.st, mc, w->x.as<uint32_t>(), stride, *nrows, false, out, mc.bytes))) return rc;
+    give_keys(k, c, keys, counts);
+    give_rows(r, rows);
     return DDS_OK;
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");

@@ -116,6 +116,9 @@ struct Worker {
   DevBuf rk_perm, rk_sums, rk_start, rk_keys, rk_lab, rk_valid, rk_mask;
   // running totals (ddshe_scan.cpp): the upper levels' planes (totals, carries), the call's row ids
   DevBuf scan_lv, scan_ids;
+  // segmented scan: the head-byte planes (two sets for a window's two scans), the call's segment starts, the
+  // windows' suffix products
+  DevBuf seg_h, seg_starts, seg_sx;
   DevBuf crt[7];  // CRT scratch of Paillier encryption and decryption (encrypt_crt_device, decrypt_crt_device)
   hipEvent_t ev[4] = {};
   // decimal codec: double-buffered pinned chunks (chars, offsets), their device copies,
@@ -656,6 +659,17 @@ int scan_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const ui
                 const uint32_t* d_list, size_t first, size_t n, bool suffix, uint32_t* O, size_t ostride);
 // the modulus' table R^k mod N, k = 0 .. F + 1 (mc.dgtab), built on first use (ddshe_groups.cpp)
 int scan_table(ModConsts& mc);
+// The segmented scan on the device (ddshe_scan.cpp; SegScanPlan of ddshe_scan_plan.hpp): scan_device's rows, the
+// product restarting at every head. heads: the head positions of the order scanned (seg_heads), from which the plan
+// counts the products; the head bytes themselves are made on the device from d_starts (nseg ascending starts, `base`
+// subtracted from each; reversed when suffix). d_list is read as given, or backwards with list_rev (a suffix scan
+// over a list that is not uploaded reversed). Synchronises the stream. With the context's timing on, the scan's
+// launches add to fold_ms and fold_launches, exactly the plan's products to fold_modmuls, the flag building to
+// total_ms.
+int seg_scan_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
+                    size_t xrows, const uint32_t* d_list, bool list_rev, size_t first, size_t n, bool suffix,
+                    const std::vector<size_t>& heads, const uint32_t* d_starts, size_t nseg, uint32_t base, uint32_t* O,
+                    size_t ostride);
 int product_tree(dds_ctx* ctx, const std::vector<uint32_t>& h, size_t count, size_t len, size_t cap16, bn::Limbs* out);
 int fold_even_modulus(dds_ctx* ctx, const bn::Limbs& M, const std::vector<bn::Limbs>& xs, const std::vector<bool>& negs,
                       bn::Limbs* out);

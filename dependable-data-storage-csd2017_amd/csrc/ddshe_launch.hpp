@@ -220,6 +220,30 @@ hipError_t launch_scan_down_rows(int S, const uint32_t* X, size_t xstride, size_
                                  uint32_t first, bool rev_in, size_t n, const uint32_t* consts, uint32_t n0,
                                  const uint32_t* tab, const uint32_t* Cin, size_t cstride, uint32_t* O, size_t ostride,
                                  size_t orows, bool rev_out, hipStream_t st);
+// The segmented scan (ddshe_scan.hip; SegScanPlan of ddshe_scan_plan.hpp): the four launches above with a head byte
+// per row of level 0 (H0, n bytes) and per total of an upper level (Hin / H, `count` bytes); the up passes also store
+// "the chunk holds a head" to Hout (one byte per chunk). list with rev_in: the list is read backwards.
+// launch_seg_heads: H0 from the ascending starts[g] - base, g < nseg <= n (reverse: 0 and n - (starts[g] - base),
+// g >= 1); launch_win_heads: H0 for blocks of w rows. launch_win_join: O[j] <- canon(Sx[j - w + 1]·O[j]) in place
+// for the rows j >= w with j % w != w - 1, 0 < w < n.
+hipError_t launch_seg_heads(const uint32_t* starts, size_t nseg, uint32_t base, size_t n, bool reverse, uint8_t* H0,
+                            hipStream_t st);
+hipError_t launch_win_heads(size_t n, size_t w, bool reverse, uint8_t* H0, hipStream_t st);
+hipError_t launch_seg_up_rows(int S, const uint32_t* X, size_t xstride, size_t xrows, const uint32_t* list,
+                              uint32_t first, bool rev_in, size_t n, const uint32_t* consts, uint32_t n0,
+                              const uint32_t* tab, const uint8_t* H0, uint32_t* T, size_t tstride, uint8_t* Hout,
+                              hipStream_t st);
+hipError_t launch_seg_up(int S, const uint32_t* Tin, size_t istride, size_t count, const uint8_t* Hin,
+                         const uint32_t* consts, uint32_t n0, uint32_t* Tout, size_t ostride, uint8_t* Hout,
+                         hipStream_t st);
+hipError_t launch_seg_carry(int S, const uint32_t* T, const uint8_t* H, uint32_t* C, size_t stride, size_t count,
+                            const uint32_t* consts, uint32_t n0, const uint32_t* Cin, size_t cstride, hipStream_t st);
+hipError_t launch_seg_down_rows(int S, const uint32_t* X, size_t xstride, size_t xrows, const uint32_t* list,
+                                uint32_t first, bool rev_in, size_t n, const uint32_t* consts, uint32_t n0,
+                                const uint32_t* tab, const uint8_t* H0, const uint32_t* Cin, size_t cstride,
+                                uint32_t* O, size_t ostride, size_t orows, bool rev_out, hipStream_t st);
+hipError_t launch_win_join(int S, const uint32_t* Sx, size_t sstride, uint32_t* O, size_t ostride, size_t n, size_t w,
+                           const uint32_t* consts, uint32_t n0, const uint32_t* tab, hipStream_t st);
 // Prime search (ddshe_prime.hpp). launch_strong1: lane t < nlanes tests row idx[t / rounds] (t / rounds when idx is
 // null) of Ncol (S1 = 20 | 40 | 56 limbs of 28 bits, odd, >= 3, at most nbits <= 28 S1 - 2 bits each) to base 2
 // (base2), to row t of Bcol, or with Bcol null to the witness of (seed, row, t % rounds), N >= 5; out[t] = 1 iff

@@ -5,6 +5,10 @@
 // totals at the rows (kernels in ddshe_scan.hpp). The host inverts nothing and combines nothing: 2 * levels + 1
 // launches and one synchronisation. The opaque rows only: it reads col->d and neither uses nor touches the digit
 // mirror.
+// Also here: the segmented scan, whose running product restarts at every segment start (dds_col_append_scan_seg,
+// dds_col_scan_seg_be, dds_segscan_plan; seg_scan_device also serves dds_col_scan_part_by_ope[_be] of
+// ddshe_groups.cpp), and the moving windows built on it (dds_col_append_window, dds_col_window_be, dds_window_plan):
+// SegScanPlan and WindowPlan of ddshe_scan_plan.hpp, the k_seg_* and k_win_* kernels.
 #include "ddshe_host.hpp"
 #include "ddshe_scan_plan.hpp"
 
@@ -70,6 +74,89 @@ int scan_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const ui
   return DDS_OK;
 }
 
+namespace {
+
+// the workspace of a segmented scan: the level planes, and `sets` sets of head-byte planes
+int seg_scan_room(Worker* w, const ModConsts& mc, const SegScanPlan& pl, size_t sets) {
+  const ScanPlan& lv = pl.lv;
+  for (size_t i = 1; i <= lv.top(); ++i)
+    if (lv.stride[i] > max_stride(mc.S))
+      return fail(DDS_E_UNSUPPORTED, "level plane exceeds the row limit of this modulus");
+  if (lv.scratch_rows) SCAN_ALLOC(w->scan_lv.ensure(lv.scratch_rows * (size_t)mc.S * 4));
+  SCAN_ALLOC(w->seg_h.ensure(sets * pl.hbytes));
+  return DDS_OK;
+}
+
+// The launches of one segmented scan, enqueued only: Hb is the plan's byte scratch with plane 0 filled. rev_in: the
+// rows are taken backwards (a list read from its end, a range from its last row); rev_out: row j goes to n - 1 - j.
+int seg_scan_launches(Worker* w, hipStream_t st, ModConsts& mc, const SegScanPlan& pl, const uint32_t* X, size_t xstride,
+                      size_t xrows, const uint32_t* d_list, size_t first, size_t n, bool rev_in, bool rev_out,
+                      uint8_t* Hb, uint32_t* O, size_t ostride) {
+  const int S = mc.S;
+  const ScanPlan& lv = pl.lv;
+  const size_t top = lv.top();
+  uint32_t* buf = w->scan_lv.as<uint32_t>();
+  auto T = [&](size_t i) { return buf + lv.t_off(i, S); };
+  auto C = [&](size_t i) { return buf + lv.c_off(i, S); };
+  auto H = [&](size_t i) { return Hb + pl.hoff[i]; };
+  const uint32_t f32 = (uint32_t)first;
+  if (top == 0) {
+    HIP_TRY(launch_seg_down_rows(S, X, xstride, xrows, d_list, f32, rev_in, n, mc.d, mc.n0, mc.dgtab, H(0), nullptr, 0,
+                                 O, ostride, n, rev_out, st));
+    return DDS_OK;
+  }
+  HIP_TRY(launch_seg_up_rows(S, X, xstride, xrows, d_list, f32, rev_in, n, mc.d, mc.n0, mc.dgtab, H(0), T(1),
+                             lv.stride[1], H(1), st));
+  for (size_t i = 1; i < top; ++i)
+    HIP_TRY(launch_seg_up(S, T(i), lv.stride[i], lv.cnt[i], H(i), mc.d, mc.n0, T(i + 1), lv.stride[i + 1], H(i + 1), st));
+  HIP_TRY(launch_seg_carry(S, T(top), H(top), C(top), lv.stride[top], lv.cnt[top], mc.d, mc.n0, nullptr, 0, st));
+  for (size_t i = top; i-- > 1;)
+    HIP_TRY(launch_seg_carry(S, T(i), H(i), C(i), lv.stride[i], lv.cnt[i], mc.d, mc.n0, C(i + 1), lv.stride[i + 1], st));
+  HIP_TRY(launch_seg_down_rows(S, X, xstride, xrows, d_list, f32, rev_in, n, mc.d, mc.n0, mc.dgtab, H(0), C(1),
+                               lv.stride[1], O, ostride, n, rev_out, st));
+  return DDS_OK;
+}
+
+// after the stream is synchronised: ev[2]..ev[3] bracket the flag building, ev[0]..ev[1] the scan
+int seg_scan_account(dds_ctx* ctx, Worker* w, size_t launches, uint64_t products) {
+  float flag_ms = 0, ms = 0;
+  HIP_TRY(hipEventElapsedTime(&flag_ms, w->ev[2], w->ev[3]));
+  HIP_TRY(hipEventElapsedTime(&ms, w->ev[0], w->ev[1]));
+  std::lock_guard<std::mutex> lk(ctx->tmu);
+  ctx->total_ms += flag_ms;
+  ctx->fold_ms += ms;
+  ctx->fold_launches += launches;
+  ctx->fold_modmuls += products;
+  return DDS_OK;
+}
+
+}  // namespace
+
+int seg_scan_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride,
+                    size_t xrows, const uint32_t* d_list, bool list_rev, size_t first, size_t n, bool suffix,
+                    const std::vector<size_t>& heads, const uint32_t* d_starts, size_t nseg, uint32_t base, uint32_t* O,
+                    size_t ostride) {
+  if (n == 0) return DDS_OK;
+  int rc;
+  if ((rc = scan_table(mc))) return rc;
+  const SegScanPlan pl(n, heads);
+  if ((rc = seg_scan_room(w, mc, pl, 1))) return rc;
+  uint8_t* Hb = w->seg_h.as<uint8_t>();
+  const bool timed = ctx->timing.load();
+  if (timed) HIP_TRY(hipEventRecord(w->ev[2], st));
+  HIP_TRY(launch_seg_heads(d_starts, nseg, base, n, suffix, Hb + pl.hoff[0], st));
+  if (timed) {
+    HIP_TRY(hipEventRecord(w->ev[3], st));
+    HIP_TRY(hipEventRecord(w->ev[0], st));
+  }
+  const bool rev_in = suffix && (!d_list || list_rev);
+  if ((rc = seg_scan_launches(w, st, mc, pl, X, xstride, xrows, d_list, first, n, rev_in, suffix, Hb, O, ostride)))
+    return rc;
+  if (timed) HIP_TRY(hipEventRecord(w->ev[1], st));
+  HIP_TRY(hipStreamSynchronize(st));  // the rows of O are complete; the caller's uploads are free again
+  return timed ? seg_scan_account(ctx, w, pl.launches, pl.products) : (int)DDS_OK;
+}
+
 }  // namespace host
 }  // namespace ddshe
 
@@ -115,9 +202,258 @@ int scan_col(dds_col* in, Worker* w, hipStream_t st, const uint64_t* row_ids, si
   return rc;
 }
 
+// seg_starts of a call of n >= 1 rows: starts[0] == 0, strictly ascending, all below n
+int seg_starts_ok(const uint64_t* starts, size_t nseg, size_t n) {
+  if (!starts || nseg == 0) return fail(DDS_E_ARG, "bad arguments");
+  if (starts[0] != 0) return fail(DDS_E_ARG, "seg_starts must begin with 0: " + std::to_string(starts[0]) + " at index 0");
+  for (size_t g = 1; g < nseg; ++g) {
+    if (starts[g] <= starts[g - 1])
+      return fail(DDS_E_ARG, "seg_starts must ascend strictly: " + std::to_string(starts[g]) + " at index " +
+                                 std::to_string(g));
+    if (starts[g] >= n)
+      return fail(DDS_E_ARG, "seg_starts must stay below n: " + std::to_string(starts[g]) + " at index " +
+                                 std::to_string(g));
+  }
+  return DDS_OK;
+}
+
+// scan_col with segments: the ids go up once (reversed for a suffix scan), the starts once as 32-bit words.
+int seg_scan_col(dds_col* in, Worker* w, hipStream_t st, const uint64_t* row_ids, size_t first, size_t n,
+                 const uint64_t* seg_starts, size_t nseg, bool suffix, uint32_t* O, size_t ostride) {
+  std::vector<uint32_t> ids32, st32(seg_starts, seg_starts + nseg);  // starts < n < 2^32
+  const uint32_t* d_list = nullptr;
+  SCAN_ALLOC(w->seg_starts.ensure(nseg * 4));
+  if (row_ids) {
+    ids32.resize(n);  // < count <= max_stride < 2^32
+    for (size_t i = 0; i < n; ++i) ids32[i] = (uint32_t)row_ids[suffix ? n - 1 - i : i];
+    SCAN_ALLOC(w->scan_ids.ensure(n * 4));
+    HIP_TRY(hipMemcpyAsync(w->scan_ids.p, ids32.data(), n * 4, hipMemcpyHostToDevice, st));
+    d_list = w->scan_ids.as<uint32_t>();
+  }
+  hipError_t e = hipMemcpyAsync(w->seg_starts.p, st32.data(), nseg * 4, hipMemcpyHostToDevice, st);
+  int rc = e == hipSuccess ? (int)DDS_OK : fail(DDS_E_HIP, std::string("upload of the segment starts: ") + hipGetErrorString(e));
+  if (!rc)
+    rc = seg_scan_device(in->ctx, w, st, *in->mc, in->d, in->stride, in->count, d_list, false, first, n, suffix,
+                         seg_heads(n, seg_starts, nseg, suffix), w->seg_starts.as<uint32_t>(), nseg, 0, O, ostride);
+  // seg_scan_device synchronises the stream on success; on an error the vectors must outlive the copies all the same
+  if (rc) (void)hipStreamSynchronize(st);
+  return rc;
+}
+
+// Rows [0, n) of O <- the moving windows of width w >= 1 over the call's rows of `in` (WindowPlan): the blocks'
+// running products to O, their suffix products to w->seg_sx, the join in place. The ids go up once, as given: the
+// suffix scan reads the list backwards. Arguments checked by the caller, who holds in->mu. Synchronises the stream.
+int window_col(dds_col* in, Worker* w, hipStream_t st, const uint64_t* row_ids, size_t first, size_t n, size_t win,
+               uint32_t* O, size_t ostride) {
+  dds_ctx* ctx = in->ctx;
+  ModConsts& mc = *in->mc;
+  const int S = mc.S;
+  int rc;
+  if ((rc = scan_table(mc))) return rc;
+  const WindowPlan wp(n, win);
+  const SegScanPlan pf(n, wp.heads_fwd), ps(n, wp.heads_rev);  // the same levels and byte planes, other heads
+  if ((rc = seg_scan_room(w, mc, pf, 2))) return rc;
+  const size_t sstride = round_up(n, 64);
+  if (wp.joined) {
+    if ((rc = check_rows(mc, n))) return rc;
+    SCAN_ALLOC(w->seg_sx.ensure((size_t)S * sstride * 4));
+  }
+  std::vector<uint32_t> ids32;
+  const uint32_t* d_list = nullptr;
+  if (row_ids) {
+    ids32.assign(row_ids, row_ids + n);  // < count <= max_stride < 2^32
+    SCAN_ALLOC(w->scan_ids.ensure(n * 4));
+    HIP_TRY(hipMemcpyAsync(w->scan_ids.p, ids32.data(), n * 4, hipMemcpyHostToDevice, st));
+    d_list = w->scan_ids.as<uint32_t>();
+  }
+  auto run = [&]() -> int {
+    uint8_t* Hf = w->seg_h.as<uint8_t>();
+    uint8_t* Hs = Hf + pf.hbytes;
+    const bool timed = ctx->timing.load();
+    if (timed) HIP_TRY(hipEventRecord(w->ev[2], st));
+    HIP_TRY(launch_win_heads(n, win, false, Hf + pf.hoff[0], st));
+    if (wp.joined) HIP_TRY(launch_win_heads(n, win, true, Hs + ps.hoff[0], st));
+    if (timed) {
+      HIP_TRY(hipEventRecord(w->ev[3], st));
+      HIP_TRY(hipEventRecord(w->ev[0], st));
+    }
+    int r = seg_scan_launches(w, st, mc, pf, in->d, in->stride, in->count, d_list, first, n, false, false, Hf, O, ostride);
+    if (r) return r;
+    if (wp.joined) {
+      uint32_t* Sx = w->seg_sx.as<uint32_t>();
+      // the level planes are reused: the stream runs the second scan after the first
+      if ((r = seg_scan_launches(w, st, mc, ps, in->d, in->stride, in->count, d_list, first, n, true, true, Hs, Sx,
+                                 sstride)))
+        return r;
+      HIP_TRY(launch_win_join(S, Sx, sstride, O, ostride, n, win, mc.d, mc.n0, mc.dgtab, st));
+    }
+    if (timed) HIP_TRY(hipEventRecord(w->ev[1], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return timed ? seg_scan_account(ctx, w, wp.launches, wp.products) : (int)DDS_OK;
+  };
+  rc = run();
+  if (rc && row_ids) (void)hipStreamSynchronize(st);  // ids32 must outlive the copy
+  return rc;
+}
+
+int window_args(const dds_col* in, size_t n, size_t w) {
+  int rc = scan_args(in, n);
+  if (rc) return rc;
+  if (w == 0) return fail(DDS_E_ARG, "a window of width 0");
+  return DDS_OK;
+}
+
+// the checks of an appending call on its two columns; the caller holds both locks
+int append_pair_ok(const dds_col* out, const dds_col* in) {
+  if (in->ctx != out->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
+  if (bn::cmp(out->mc->N, in->mc->N) != 0 || out->mc->S != in->mc->S || out->mc->W != in->mc->W)
+    return fail(DDS_E_ARG, "columns must be over the same modulus");
+  return DDS_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int dds_segscan_plan(size_t n, const uint64_t* seg_starts, size_t nseg, int suffix, int* fan, int* levels,
+                     uint64_t* products, uint64_t* workspace_rows) {
+  try {
+    if (n > (size_t)0xFFFFFFFFu) return fail(DDS_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
+    uint64_t pr = 0, ws = 0;
+    int lv = 0;
+    if (n) {
+      int rc = seg_starts_ok(seg_starts, nseg, n);
+      if (rc) return rc;
+      const SegScanPlan pl(n, seg_heads(n, seg_starts, nseg, suffix != 0));
+      lv = (int)pl.lv.top();
+      pr = pl.products;
+      ws = pl.lv.scratch_rows;
+    }
+    if (fan) *fan = (int)kScanFan;
+    if (levels) *levels = lv;
+    if (products) *products = pr;
+    if (workspace_rows) *workspace_rows = ws;
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_window_plan(size_t n, size_t w, int* fan, int* levels, uint64_t* products, uint64_t* workspace_rows) {
+  try {
+    if (n > (size_t)0xFFFFFFFFu) return fail(DDS_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
+    if (w == 0) return fail(DDS_E_ARG, "a window of width 0");
+    const WindowPlan wp(n, w);
+    if (fan) *fan = (int)kScanFan;
+    if (levels) *levels = wp.levels;
+    if (products) *products = wp.products;
+    if (workspace_rows) *workspace_rows = wp.workspace_rows;
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_append_scan_seg(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n,
+                            const uint64_t* seg_starts, size_t nseg, int suffix) {
+  try {
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    int rc = scan_args(in, n);
+    if (rc) return rc;
+    if (out == in) return fail(DDS_E_ARG, "out and the source column must differ");
+    if (n == 0) return DDS_OK;
+    if ((rc = seg_starts_ok(seg_starts, nseg, n))) return rc;
+    ColWriteLock lk(out, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lr(in->mu, std::defer_lock);  // `in` is only read
+    std::lock(lk.lk, lr);
+    lk.touches_from(out->count);  // an append
+    if ((rc = append_pair_ok(out, in))) return rc;
+    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
+    if (n > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
+    WorkerLease wl(in->ctx);
+    if ((rc = wl.acquire())) return rc;
+    // rows past the count: nothing is published unless the call succeeds
+    if ((rc = seg_scan_col(in, wl.w, wl.st, row_ids, first, n, seg_starts, nseg, suffix != 0, out->d + out->count,
+                           out->stride)))
+      return rc;
+    out->count += n;
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_scan_seg_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, const uint64_t* seg_starts,
+                        size_t nseg, int suffix, uint8_t* out) {
+  try {
+    int rc = scan_args(in, n);
+    if (rc) return rc;
+    if (n == 0) return DDS_OK;  // nothing to write: out may be NULL
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    if ((rc = seg_starts_ok(seg_starts, nseg, n))) return rc;
+    std::shared_lock<std::shared_mutex> lk(in->mu);
+    ModConsts& mc = *in->mc;
+    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
+    if ((rc = check_rows(mc, n))) return rc;
+    WorkerLease wl(in->ctx);
+    if ((rc = wl.acquire())) return rc;
+    Worker* w = wl.w;
+    const size_t stride = round_up(n, 64);
+    SCAN_ALLOC(w->x.ensure((size_t)mc.S * stride * 4));
+    if ((rc = seg_scan_col(in, w, wl.st, row_ids, first, n, seg_starts, nseg, suffix != 0, w->x.as<uint32_t>(), stride)))
+      return rc;
+    return rows_to_be(w, wl.st, mc, w->x.as<uint32_t>(), stride, n, false, out, mc.bytes);
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_append_window(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n, size_t w) {
+  try {
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    int rc = window_args(in, n, w);
+    if (rc) return rc;
+    if (out == in) return fail(DDS_E_ARG, "out and the source column must differ");
+    if (n == 0) return DDS_OK;
+    ColWriteLock lk(out, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lr(in->mu, std::defer_lock);  // `in` is only read
+    std::lock(lk.lk, lr);
+    lk.touches_from(out->count);  // an append
+    if ((rc = append_pair_ok(out, in))) return rc;
+    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
+    if (n > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
+    WorkerLease wl(in->ctx);
+    if ((rc = wl.acquire())) return rc;
+    // rows past the count: nothing is published unless the call succeeds
+    if ((rc = window_col(in, wl.w, wl.st, row_ids, first, n, w, out->d + out->count, out->stride))) return rc;
+    out->count += n;
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_window_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, size_t w, uint8_t* out) {
+  try {
+    int rc = window_args(in, n, w);
+    if (rc) return rc;
+    if (n == 0) return DDS_OK;  // nothing to write: out may be NULL
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    std::shared_lock<std::shared_mutex> lk(in->mu);
+    ModConsts& mc = *in->mc;
+    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
+    if ((rc = check_rows(mc, n))) return rc;
+    WorkerLease wl(in->ctx);
+    if ((rc = wl.acquire())) return rc;
+    Worker* wk = wl.w;
+    const size_t stride = round_up(n, 64);
+    SCAN_ALLOC(wk->x.ensure((size_t)mc.S * stride * 4));
+    if ((rc = window_col(in, wk, wl.st, row_ids, first, n, w, wk->x.as<uint32_t>(), stride))) return rc;
+    return rows_to_be(wk, wl.st, mc, wk->x.as<uint32_t>(), stride, n, false, out, mc.bytes);
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
 
 int dds_scan_plan(size_t n, int* fan, int* levels, uint64_t* products, uint64_t* workspace_rows) {
   try {

@@ -75,6 +75,8 @@ EXPORTS = [
     "dds_col_fold_groups", "dds_col_fold_groups_be", "dds_fold_groups_plan",
     "dds_ope_rank", "dds_ope_rank_device", "dds_col_fold_by_ope", "dds_col_fold_by_ope_be",
     "dds_col_append_scan", "dds_col_scan_be", "dds_scan_plan", "dds_col_scan_by_ope", "dds_col_scan_by_ope_be",
+    "dds_col_append_scan_seg", "dds_col_scan_seg_be", "dds_segscan_plan", "dds_col_scan_part_by_ope",
+    "dds_col_scan_part_by_ope_be", "dds_col_append_window", "dds_col_window_be", "dds_window_plan",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -200,6 +202,16 @@ _sig("dds_col_scan_be", C.c_int, C.c_void_p, _u64p, _sz, _sz, C.c_int, _u8p)
 _sig("dds_scan_plan", C.c_int, _sz, C.POINTER(C.c_int), C.POINTER(C.c_int), _u64p, _u64p)
 _sig("dds_col_scan_by_ope", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_int, C.c_void_p, _i64p, _u64p, _sz, _szp)
 _sig("dds_col_scan_by_ope_be", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_int, _u8p, _i64p, _u64p, _sz, _szp)
+_sig("dds_col_append_scan_seg", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, _sz, _u64p, _sz, C.c_int)
+_sig("dds_col_scan_seg_be", C.c_int, C.c_void_p, _u64p, _sz, _sz, _u64p, _sz, C.c_int, _u8p)
+_sig("dds_segscan_plan", C.c_int, _sz, _u64p, _sz, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _u64p, _u64p)
+_sig("dds_col_scan_part_by_ope", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_int, C.c_void_p, _u64p, _sz, _i64p,
+     _u64p, _sz, _szp, _szp)
+_sig("dds_col_scan_part_by_ope_be", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_int, _u8p, _u64p, _sz, _i64p,
+     _u64p, _sz, _szp, _szp)
+_sig("dds_col_append_window", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, _sz, _sz)
+_sig("dds_col_window_be", C.c_int, C.c_void_p, _u64p, _sz, _sz, _sz, _u8p)
+_sig("dds_window_plan", C.c_int, _sz, _sz, C.POINTER(C.c_int), C.POINTER(C.c_int), _u64p, _u64p)
 _sig("dds_pair_modmul_dec", C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _sz, _szp)
 _sig("dds_pair_stats", C.c_int, C.c_void_p, _u64p, _u64p)
 _sig("dds_pair_timing", C.c_int, C.c_void_p, _u64p, _u64p, _u64p, _u64p)
@@ -778,6 +790,25 @@ class Engine:
         _check(_lib.dds_scan_plan(n, C.byref(f), C.byref(lv), C.byref(pr), C.byref(ws)), "dds_scan_plan")
         return f.value, lv.value, pr.value, ws.value
 
+    @staticmethod
+    def segscan_plan(n: int, seg_starts, suffix: bool = False) -> tuple:
+        """dds_segscan_plan: (fan, levels, products, workspace rows) of the segmented running totals of n rows
+        whose segments begin at the positions seg_starts; the products are exact for this head pattern. No GPU
+        work."""
+        st = np.ascontiguousarray(seg_starts, dtype=np.uint64)
+        f, lv, pr, ws = C.c_int(), C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(_lib.dds_segscan_plan(n, st.ctypes.data_as(_u64p), len(st), int(bool(suffix)), C.byref(f), C.byref(lv),
+                                     C.byref(pr), C.byref(ws)), "dds_segscan_plan")
+        return f.value, lv.value, pr.value, ws.value
+
+    @staticmethod
+    def window_plan(n: int, w: int) -> tuple:
+        """dds_window_plan: (fan, levels, products, workspace rows) of the moving windows of width w over n rows.
+        No GPU work."""
+        f, lv, pr, ws = C.c_int(), C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(_lib.dds_window_plan(n, w, C.byref(f), C.byref(lv), C.byref(pr), C.byref(ws)), "dds_window_plan")
+        return f.value, lv.value, pr.value, ws.value
+
     def host_register(self, arr: np.ndarray):
         """dds_host_register: page-lock a reusable output array (results DMA'd straight into it)."""
         _check(_lib.dds_host_register(self._h, arr.ctypes.data_as(C.c_void_p), arr.nbytes), "dds_host_register")
@@ -1142,6 +1173,92 @@ class Column(_Mutable):
             col._h, by._h, m, mw, int(bool(suffix)), self._h, keys, counts, cap, ng))
         _check(rc, "dds_col_scan_by_ope")
         return keys, counts
+
+    def _rows_of(self, out, n):
+        raw = C.string_at(C.addressof(out), self.mb * n)
+        return [int.from_bytes(raw[j * self.mb:(j + 1) * self.mb], "big") for j in range(n)]
+
+    def append_scan_seg(self, src: "Column", seg_starts, row_ids=None, first: int = 0, count: int | None = None,
+                        suffix: bool = False):
+        """dds_col_append_scan_seg: append the running totals of src's rows, restarting at every position of
+        seg_starts (positions in the call's order, the first 0, strictly ascending): row j = the product of the
+        rows from its segment's start through j, with suffix from j through its segment's last row."""
+        ids, n = src._scan_args(row_ids, first, count)
+        st = np.ascontiguousarray(seg_starts, dtype=np.uint64)
+        _check(_lib.dds_col_append_scan_seg(self._h, src._h, None if ids is None else ids.ctypes.data_as(_u64p), first,
+                                            n, st.ctypes.data_as(_u64p), len(st), int(bool(suffix))),
+               "dds_col_append_scan_seg")
+
+    def scan_seg(self, seg_starts, row_ids=None, first: int = 0, count: int | None = None,
+                 suffix: bool = False) -> list:
+        """dds_col_scan_seg_be: the same segmented running totals as a list of canonical residues."""
+        ids, n = self._scan_args(row_ids, first, count)
+        st = np.ascontiguousarray(seg_starts, dtype=np.uint64)
+        out = (C.c_uint8 * (self.mb * max(1, n)))()
+        _check(_lib.dds_col_scan_seg_be(self._h, None if ids is None else ids.ctypes.data_as(_u64p), first, n,
+                                        st.ctypes.data_as(_u64p), len(st), int(bool(suffix)), out),
+               "dds_col_scan_seg_be")
+        return self._rows_of(out, n)
+
+    def append_window(self, src: "Column", w: int, row_ids=None, first: int = 0, count: int | None = None):
+        """dds_col_append_window: append the moving windows of width w over src's rows: row j = the product of the
+        rows max(0, j - w + 1) .. j. No inverse is taken: zero rows and non-units are served."""
+        ids, n = src._scan_args(row_ids, first, count)
+        _check(_lib.dds_col_append_window(self._h, src._h, None if ids is None else ids.ctypes.data_as(_u64p), first,
+                                          n, w), "dds_col_append_window")
+
+    def window(self, w: int, row_ids=None, first: int = 0, count: int | None = None) -> list:
+        """dds_col_window_be: the same moving windows as a list of canonical residues."""
+        ids, n = self._scan_args(row_ids, first, count)
+        out = (C.c_uint8 * (self.mb * max(1, n)))()
+        _check(_lib.dds_col_window_be(self._h, None if ids is None else ids.ctypes.data_as(_u64p), first, n, w, out),
+               "dds_col_window_be")
+        return self._rows_of(out, n)
+
+    @staticmethod
+    def _part_by_ope(by: "OpeColumn", mask, call):
+        """call(mask pointer, mask words, rows, cap_rows, keys, counts, cap_groups, nrows, ngroups) -> status, with
+        room for every row of `by` and up to 4,096 groups; more groups are asked for again at the size the engine
+        reports (DDS_E_BUFSIZE wrote nothing). Returns (status, rows, keys, counts)."""
+        words = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint64)
+        cap_rows, cap_groups = max(1, len(by)), max(1, min(len(by), 4096))
+        nr, ng = C.c_size_t(), C.c_size_t()
+        while True:
+            rows = np.empty(cap_rows, dtype=np.uint64)
+            keys, counts = np.empty(cap_groups, dtype=np.int64), np.empty(cap_groups, dtype=np.uint64)
+            rc = call(None if words is None else words.ctypes.data_as(_u64p), 0 if words is None else len(words),
+                      rows.ctypes.data_as(_u64p), cap_rows, keys.ctypes.data_as(_i64p), counts.ctypes.data_as(_u64p),
+                      cap_groups, C.byref(nr), C.byref(ng))
+            if rc != DDS_E_BUFSIZE or (ng.value <= cap_groups and nr.value <= cap_rows):
+                return rc, rows[:nr.value], keys[:ng.value], counts[:ng.value]
+            cap_rows, cap_groups = max(cap_rows, nr.value), max(cap_groups, ng.value)
+
+    def scan_part_by_ope(self, by: "OpeColumn", mask=None, suffix: bool = False):
+        """dds_col_scan_part_by_ope_be: SELECT row, SUM(x) OVER (PARTITION BY key ORDER BY row) with the keys in
+        the resident OPE column `by`; participation and mask as fold_by_ope. Returns (rows, values, keys, counts):
+        slot t is the t-th participating row in (key, row id) order, rows[t] its id, values[t] the product mod N
+        of the participating rows of its key with row id <= it (suffix: >= it); keys ascending, counts[g] the rows
+        of key g, whose slots start at counts[:g].sum()."""
+        out = None
+
+        def call(m, mw, rows, cap_rows, keys, counts, cap_groups, nr, ng):
+            nonlocal out
+            out = (C.c_uint8 * (self.mb * cap_rows))()
+            return _lib.dds_col_scan_part_by_ope_be(self._h, by._h, m, mw, int(bool(suffix)), out, rows, cap_rows, keys,
+                                                    counts, cap_groups, nr, ng)
+
+        rc, rows, keys, counts = self._part_by_ope(by, mask, call)
+        _check(rc, "dds_col_scan_part_by_ope_be")
+        return rows, self._rows_of(out, len(rows)), keys, counts
+
+    def append_scan_part_by_ope(self, col: "Column", by: "OpeColumn", mask=None, suffix: bool = False):
+        """dds_col_scan_part_by_ope: the same values of col's rows appended to this column, slot t at the old
+        len(self) + t, canonical and live; returns (rows, keys, counts)."""
+        rc, rows, keys, counts = self._part_by_ope(
+            by, mask, lambda m, mw, rows, cap_rows, keys, counts, cap_groups, nr, ng: _lib.dds_col_scan_part_by_ope(
+                col._h, by._h, m, mw, int(bool(suffix)), self._h, rows, cap_rows, keys, counts, cap_groups, nr, ng))
+        _check(rc, "dds_col_scan_part_by_ope")
+        return rows, keys, counts
 
     def fold_partial_device(self, d_partial: int, first: int = 0, count: int | None = None):
         """dds_col_fold_partial_device: the partial (partial_words u32) into device memory at d_partial."""

@@ -422,6 +422,19 @@ class ResidentStore:
         element's VALUE on the GPU (dds_col_fold_by_ope_be): no per-row host work, the mask is the only per-row
         upload. descending (not None): the cumulative values instead (dds_col_scan_by_ope_be): over the keys up to
         each key (False), or from each key on (True)"""
+        oc = self._by_ope_column(c, by_position, modulus)
+        try:
+            mask = self._where_mask(where)
+            if descending is None:
+                keys, vals, _ = c.col.fold_by_ope(oc, mask)
+            else:
+                keys, vals, _ = c.col.scan_by_ope(oc, mask, suffix=descending)
+        except DDSError as e:
+            raise ServerError(str(e)) from e
+        return {int(k): str(v) for k, v in zip(keys, vals)}
+
+    def _by_ope_column(self, c: _CipherColumn | None, by_position: int, modulus: int):
+        """the resident OPE column a keyed call over column c groups by; 500 / 404 as _fold_by"""
         if c is None or modulus != c.modulus:
             raise ServerError("no resident column at this position under this modulus")
         oc = self.ope.get(by_position)
@@ -431,21 +444,54 @@ class ResidentStore:
             raise ServerError("NumberFormatException: a qualifying element is not an integer")
         if c.nlive == 0:
             raise NotFound()
+        return oc
+
+    def _where_mask(self, where):
+        """the row mask of a keyed call's `where` (route, position, value), or None; DDSError from the search"""
+        if where is None:
+            return None
+        route, position, value = where
+        wc = self.ope.get(position)
+        if wc is None:
+            raise ServerError("no resident OPE column at the WHERE position")
+        mask, _ = wc.search_mask(_dec_text(value), routes._ROUTE_OP[route])
+        return mask
+
+    def _scan_part_by_ope(self, c: _CipherColumn | None, by_position: int, modulus: int, where,
+                          descending: bool) -> dict[int, list]:
+        """the running totals of column c inside each key of the resident OPE column at by_position
+        (dds_col_scan_part_by_ope_be): the rows _fold_by_ope takes, with its errors; {key: [(stored-set key,
+        decimal text), ...]} in row order"""
+        oc = self._by_ope_column(c, by_position, modulus)
         try:
-            mask = None
-            if where is not None:
-                route, position, value = where
-                wc = self.ope.get(position)
-                if wc is None:
-                    raise ServerError("no resident OPE column at the WHERE position")
-                mask, _ = wc.search_mask(_dec_text(value), routes._ROUTE_OP[route])
-            if descending is None:
-                keys, vals, _ = c.col.fold_by_ope(oc, mask)
-            else:
-                keys, vals, _ = c.col.scan_by_ope(oc, mask, suffix=descending)
+            rows, vals, keys, counts = c.col.scan_part_by_ope(oc, self._where_mask(where), suffix=descending)
         except DDSError as e:
             raise ServerError(str(e)) from e
-        return {int(k): str(v) for k, v in zip(keys, vals)}
+        out, at = {}, 0
+        for k, cnt in zip(keys, counts):
+            out[int(k)] = [(self.keys[int(rows[t])], str(vals[t])) for t in range(at, at + int(cnt))]
+            at += int(cnt)
+        return out
+
+    def running_sum_partition_by_ope(self, position: int, by_position: int, nsqr: str, where=None,
+                                     descending: bool = False) -> dict[int, list]:
+        """SELECT row, SUM(x) OVER (PARTITION BY key ORDER BY row) [WHERE ...]: {value of the OPE element at
+        by_position: [(stored-set key, Enc(sum of m over the partition's rows up to this one) as decimal text),
+        ...] in row order}, over the rows sum_all_by_ope groups and with its `where`. descending: the rows from
+        this one on. One labelling and one segmented scan on the GPU."""
+        x = _bigint(nsqr)
+        if x is None:
+            raise ServerError("NumberFormatException: nsqr")
+        return self._scan_part_by_ope(self.by_pos_sum.get(position), by_position, x, where, bool(descending))
+
+    def running_mult_partition_by_ope(self, position: int, by_position: int, pubkey: str, where=None,
+                                      descending: bool = False) -> dict[int, list]:
+        """The running MultAll inside each key, as running_sum_partition_by_ope, under the modulus of pubkey."""
+        try:
+            n = rsa_modulus(pubkey)
+        except ValueError as e:
+            raise ServerError(f"InvalidKeySpecException: {e}") from e
+        return self._scan_part_by_ope(self.by_pos_mult.get(position), by_position, n, where, bool(descending))
 
     def sum_all_by_ope(self, position: int, by_position: int, nsqr: str, where=None) -> dict[int, str]:
         """SELECT key, SUM(x) [WHERE ...] GROUP BY key: {value of the OPE element at by_position: Enc(sum of the

@@ -741,6 +741,56 @@ int dds_col_scan_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size
 int dds_col_scan_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
                            uint8_t* out, int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups);
 
+/* ---- partitioned running totals and moving windows: the segmented scan ----------
+ * The running totals above, restarting at a boundary (SUM(x) OVER (PARTITION BY key ORDER BY ...)): seg_starts holds
+ * the nseg positions, in the call's order, at which a segment begins: seg_starts[0] == 0, strictly ascending, all
+ * below n; anything else is DDS_E_ARG and dds_last_error names the index. out row j = the product of the rows from
+ * its segment's start through j; with suffix != 0, from j through its segment's last row. out row j always belongs
+ * to input j; canonical, positional, liveness ignored, a repeated id counts twice: all as dds_col_append_scan, and
+ * so are the checks, the errors, the locking, DDS_E_NOMEM and DDS_E_UNSUPPORTED. n == 0: DDS_OK, nothing read. A
+ * zero row zeroes the rest of its own segment only.
+ * The same chunks, levels and launches as the unsegmented scan (2 * levels + 1, one synchronisation), with a head
+ * byte per row, made on the device from the starts (one upload of the ids, one of the starts as 32-bit words), and
+ * a byte per chunk total, "the chunk holds a head": at a head the running product is replaced by the row, a flagged
+ * total replaces the carry, both a load in place of a product. Timing: the launches add to fold_ms / launches,
+ * exactly dds_segscan_plan's products to dds_ctx_get_fold_work's modmuls, the flag building to total_ms. */
+int dds_col_append_scan_seg(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n,
+                            const uint64_t* seg_starts, size_t nseg, int suffix);
+int dds_col_scan_seg_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, const uint64_t* seg_starts,
+                        size_t nseg, int suffix, uint8_t* out);
+/* What that call does: fan, levels and workspace_rows as dds_scan_plan(n), and the exact Montgomery products for
+ * this head pattern (heads and flagged totals save products; one segment: dds_scan_plan's figure). seg_starts is
+ * checked as above (n == 0: not read, everything 0). Every output is nullable. No GPU work. */
+int dds_segscan_plan(size_t n, const uint64_t* seg_starts, size_t nseg, int suffix, int* fan, int* levels,
+                     uint64_t* products, uint64_t* workspace_rows);
+/* SELECT row, SUM(x) OVER (PARTITION BY key ORDER BY row) [WHERE mask] with the keys in the resident OPE column:
+ * participation, keys[g], counts[g] (the rows of key g, not cumulative), errors and locking exactly as
+ * dds_col_fold_by_ope. Output slot t is the t-th participating row in (key ascending, row id ascending) order, the
+ * valid tail of the device's sorted permutation as it stands: rows[t] is its row id (read back in the copy that
+ * brings keys and counts), its value the product of the participating rows of the same key with row id <= rows[t]
+ * (suffix != 0: >= rows[t]), canonical. Partition g occupies the slots from counts[0] + ... + counts[g-1] on.
+ * *nrows > cap_rows or *ngroups > cap_groups: DDS_E_BUFSIZE, both set to what is required, nothing written or
+ * appended. No participating row: DDS_OK with both 0. rows, keys, counts are nullable. Nothing per row goes up but
+ * the optional mask: the head bytes come from the ranks' segment starts on the device. The column form appends
+ * *nrows rows. Timing: labelling and flags add to total_ms, the scan to fold_ms / launches / modmuls. */
+int dds_col_scan_part_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
+                             dds_col* out, uint64_t* rows, size_t cap_rows, int64_t* keys, uint64_t* counts,
+                             size_t cap_groups, size_t* nrows, size_t* ngroups);
+int dds_col_scan_part_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, int suffix,
+                                uint8_t* out, uint64_t* rows, size_t cap_rows, int64_t* keys, uint64_t* counts,
+                                size_t cap_groups, size_t* nrows, size_t* ngroups);
+/* Moving windows: out row j = the product of the rows max(0, j - w + 1) .. j of the call, canonical; rows, checks,
+ * errors and locking as dds_col_append_scan. w == 0: DDS_E_ARG; w >= n: the plain running totals. No inverse is
+ * taken, so zero rows and non-units (an RSA row sharing a factor with N) are served exactly: the rows are cut into
+ * blocks of w; P, the running product inside each block, goes straight to the destination, Sx, the suffix product
+ * inside each block, to a scratch of n rows, and a join kernel rewrites in place the rows with j >= w and
+ * j % w != w - 1 as Sx[j - w + 1] * P[j], two Montgomery products each. Windows clipped at partition boundaries
+ * are not offered. dds_window_plan: levels of one scan, the products of all of it (what timing adds to modmuls)
+ * and the scratch rows, Sx included; w == 1 and w >= n run the scan of P alone. */
+int dds_col_append_window(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n, size_t w);
+int dds_col_window_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, size_t w, uint8_t* out);
+int dds_window_plan(size_t n, size_t w, int* fan, int* levels, uint64_t* products, uint64_t* workspace_rows);
+
 /* ---- device-resident batched encryption (BASELINE.json config 4) --------------
  * dds_col_fill_random: append `count` seeded random rows r < 2^bits (odd, so r != 0):
  *   limb l of row i = splitmix64(splitmix64(seed ^ (row0+i)) + l) in the column's rW layout.
