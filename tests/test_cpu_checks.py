@@ -55,6 +55,15 @@ CHECKS = {
         + ["ok " + case for case in ("window plans", "table columns and the 2^32 bound", "bucket digits",
                                      "weighted edges (Q no unit")],
         extra=lambda lines: not any(ln.startswith("FAIL") for ln in lines)),
+    # the lane-faithful replay of Mont / Grp and the word-faithful replay of Sos (csrc/check_lanes.hpp,
+    # csrc/check_sos.hpp) on seeded and capacity operands; tests/test_carry_check.py drives their rare paths
+    "carry_check": dict(
+        prefixes=[f"ok lanes ({s}, {tpi}, {w}) {form}" for s, tpi, w in
+                  ((40, 2, 28), (74, 2, 28), (76, 2, 28), (112, 4, 28), (148, 4, 28), (232, 8, 27), (320, 16, 27),
+                   (640, 32, 27), (48, 16, 28), (80, 16, 28), (112, 16, 28), (160, 16, 28), (240, 16, 27))
+                  for form in ("plain", "QP")]
+        + [f"ok sos ({s}, {w})" for s, w in ((46, 26), (84, 26), (86, 26), (124, 26), (162, 26), (244, 26),
+                                             (336, 26), (694, 25))]),
 }
 
 
