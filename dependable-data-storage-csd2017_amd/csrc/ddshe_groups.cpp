@@ -11,10 +11,14 @@
 // cumulative SUM by key (dds_col_scan_by_ope[_be]): the same labelling and fold into a workspace, then one scan of
 // the group totals (scan_device of ddshe_scan.cpp). And the running totals inside each key
 // (dds_col_scan_part_by_ope[_be]): the same labelling, then one segmented scan over the sorted permutation
-// (seg_scan_device of ddshe_scan.cpp).
+// (seg_scan_device of ddshe_scan.cpp). And the grouped fold keyed by a string element of the resident string table
+// (dds_col_fold_by_str[_be]): the same sort and ranks over a salted digest of the bytes, verified byte for byte on
+// the device and repeated under another salt on a collision (ddshe_strkey.hip), the groups in order of first
+// occurrence.
 #include "ddshe_groups_plan.hpp"
 #include "ddshe_host.hpp"
 #include "ddshe_scan_plan.hpp"
+#include "ddshe_strkey.hpp"
 
 using namespace ddshe;
 using namespace ddshe::host;
@@ -321,6 +325,164 @@ int fold_by_ope_rows(const dds_col* col, const OpeKeys& K, const uint64_t* mask,
   if (K.n_bad) return fail(DDS_E_FORMAT, "NumberFormatException: a live key element is not an integer");
   if (K.n_wide) return fail(DDS_E_UNSUPPORTED, "a live key element is outside int64");
   return DDS_OK;
+}
+
+// DDSHE_STRKEY_BITS=<1..64> (read on every call): the top bits of the digest the FIRST pass of a grouping by strings
+// sorts by; fewer than 64 makes first-pass collisions, so the verification and the salt loop can be driven
+int strkey_first_bits() {
+  if (const char* e = getenv("DDSHE_STRKEY_BITS")) {
+    const int v = atoi(e);
+    if (v >= 1 && v <= 64) return v;
+  }
+  return 64;
+}
+
+// The labelling of a call keyed by a resident string table, label_by_ope's outputs from text: the optional mask goes
+// up; then per pass the key kernel (valid byte and salted digest of the element at `position`), the sort, the rank
+// kernels and the verification, whose mismatch count comes back in one small read; a pass that found none proves the
+// segments are the classes of equal strings (ddshe_strkey.hpp) and ends the loop, another runs under the next salt.
+// *ng <- the distinct strings among the participating rows, their sizes are enqueued into *d_cnt, the permutation
+// lies in w->rk_perm, the segment starts in w->rk_start, all in digest order. *passes <- the passes run. A mismatch
+// in the last pass: DDS_E_UNSUPPORTED. timed: w->ev[2] is recorded before the first pass.
+int label_by_str(dds_col* col, const StrKeys& K, size_t position, Worker* w, hipStream_t st, const uint64_t* mask,
+                 bool timed, size_t* ng, const uint32_t** d_cnt, int* passes) {
+  const size_t n = K.count, words = (n + 63) / 64;
+  int rc;
+  if ((rc = groups_table(*col->mc))) return rc;
+  GRP_ALLOC(w->rk_valid.ensure(n));
+  GRP_ALLOC(w->sk_key.ensure(n * 8));
+  GRP_ALLOC(w->sk_ctr.ensure(4));
+  const uint64_t* d_mask = nullptr;
+  if (mask) {
+    GRP_ALLOC(w->rk_mask.ensure(words * 8));
+    HIP_TRY(hipMemcpyAsync(w->rk_mask.p, mask, words * 8, hipMemcpyHostToDevice, st));  // one bit per row
+    d_mask = w->rk_mask.as<uint64_t>();
+  }
+  if (timed) HIP_TRY(hipEventRecord(w->ev[2], st));
+  const int first_bits = strkey_first_bits();
+  for (int pass = 0; pass < kStrKeyPasses; ++pass) {
+    *passes = pass + 1;
+    HIP_TRY(launch_strkey(K.d_row_beg, K.d_row_len, K.d_live, K.d_elem_off, K.d_chars, K.nheap, K.nchars, position,
+                          col->ndead ? col->dlive : nullptr, d_mask, n, (uint64_t)pass,
+                          strkey_pass_bits(pass, first_bits), w->rk_valid.as<uint8_t>(), w->sk_key.as<int64_t>(), st));
+    if ((rc = rank_device(w, st, w->sk_key.as<int64_t>(), w->rk_valid.as<uint8_t>(), n, nullptr, nullptr, nullptr, true,
+                          nullptr, ng, d_cnt)))
+      return rc;
+    if (*ng == 0) return DDS_OK;  // no participating row: nothing to verify
+    HIP_TRY(launch_strkey_verify(w->rk_perm.as<uint32_t>(), w->rk_valid.as<uint8_t>(), w->sk_key.as<int64_t>(), n,
+                                 K.d_row_beg, K.d_row_len, K.d_elem_off, K.d_chars, K.nheap, K.nchars, position,
+                                 w->sk_ctr.as<uint32_t>(), st));
+    uint32_t bad = 0;
+    HIP_TRY(read_sync(w, st, w->sk_ctr.p, &bad, 4));
+    if (bad == 0) return DDS_OK;
+  }
+  return fail(DDS_E_UNSUPPORTED, "digest collisions among the group keys under every salt");
+}
+
+// The grouped fold of `col` keyed by element `position` of the resident string table K (dds_col_fold_by_str[_be]);
+// the caller holds both locks and has checked the arguments. label_by_str's segments are in digest order; the groups'
+// order is the data's: the same sort over the segments' first rows gives ord (group g is segment ord[g]) and its
+// inverse. The fold runs over the permutation's valid tail as it stands, in digest order, into w->x, and
+// launch_scatter_rows places segment s at row inv[s] of what dest names: ngroups rows move, not the id list's n.
+// *ngroups <- the distinct strings among the participating rows; above cap: DDS_E_BUFSIZE before anything is written.
+// hfirst / hcounts: each group's smallest row id and size in the groups' order, filled on success only.
+template <class Dest>
+int fold_by_str_device(dds_col* col, const StrKeys& K, size_t position, Worker* w, hipStream_t st, const uint64_t* mask,
+                       size_t cap, size_t* ngroups, int* passes, std::vector<uint32_t>* hfirst,
+                       std::vector<uint32_t>* hcounts, Dest dest) {
+  dds_ctx* ctx = col->ctx;
+  ModConsts& mc = *col->mc;
+  const size_t n = K.count;
+  const bool timed = ctx->timing.load();
+  int rc, np = 0;
+  size_t ng = 0;
+  const uint32_t* d_cnt = nullptr;
+  if ((rc = label_by_str(col, K, position, w, st, mask, timed, &ng, &d_cnt, &np))) return rc;
+  *ngroups = ng;
+  if (passes) *passes = np;
+  if (ng > cap) {
+    HIP_TRY(hipStreamSynchronize(st));  // the counts kernel is done with the worker's buffers
+    return fail(DDS_E_BUFSIZE, std::to_string(ng) + " groups, room for " + std::to_string(cap));
+  }
+  if (ng == 0) return DDS_OK;
+  if ((rc = check_rows(mc, ng))) return rc;
+  const size_t tstride = round_up(ng, 64);
+  GRP_ALLOC(w->rk_keys.ensure(ng * 8));
+  GRP_ALLOC(w->sk_ord.ensure(ng * 4));
+  GRP_ALLOC(w->sk_inv.ensure(ng * 4));
+  GRP_ALLOC(w->tab.ensure(rs_scratch_bytes(ng)));
+  GRP_ALLOC(w->x.ensure((size_t)mc.S * tstride * 4));
+  MappedWords ow;
+  HIP_TRY(mapped_words(w, &ow));
+  HIP_TRY(launch_strkey_order(w->rk_perm.as<uint32_t>(), w->rk_start.as<uint32_t>(), ng, n, w->rk_keys.as<int64_t>(),
+                              st));
+  HIP_TRY(launch_ope_order(w->rk_keys.as<int64_t>(), nullptr, ng, 0, w->tab.p, w->sk_ord.as<uint32_t>(), st, nullptr,
+                           &ow));
+  HIP_TRY(launch_strkey_inv(w->sk_ord.as<uint32_t>(), ng, w->sk_inv.as<uint32_t>(), st));
+  if (timed) HIP_TRY(hipEventRecord(w->ev[3], st));
+  // first rows, sizes and the order through the pinned read-back buffer, one after the other
+  GRP_ALLOC(w->hbig.ensure(ng * 16));
+  int64_t* pf = (int64_t*)w->hbig.p;
+  uint32_t* pc = (uint32_t*)(pf + ng);
+  uint32_t* po = pc + ng;
+  HIP_TRY(hipMemcpyAsync(pf, w->rk_keys.p, ng * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(pc, d_cnt, ng * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(po, w->sk_ord.p, ng * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const std::vector<uint32_t> cnt(pc, pc + ng);  // digest order: what the fold's plan takes
+  std::vector<uint32_t> first(ng), sizes(ng);
+  std::vector<bool> seen(ng, false);
+  size_t nvalid = 0;
+  for (size_t g = 0; g < ng; ++g) {
+    const uint32_t s = po[g];
+    if (s >= ng || seen[s] || pf[s] < 0 || (uint64_t)pf[s] >= n || cnt[s] == 0)
+      return fail(DDS_E_HIP, "the groups' order is no permutation of the segments");
+    seen[s] = true;
+    first[g] = (uint32_t)pf[s];
+    sizes[g] = cnt[s];
+    nvalid += cnt[s];
+  }
+  if (nvalid > n) return fail(DDS_E_HIP, "group sizes exceed the table's rows");
+  uint32_t* O = nullptr;
+  size_t ostride = 0;
+  if ((rc = dest(ng, &O, &ostride))) return rc;
+  // the invalid rows come first in the permutation: the participating ones are its last nvalid slots
+  if ((rc = fold_segments(col, w, st, w->rk_perm.as<uint32_t>() + (n - nvalid), nvalid, cnt.data(), d_cnt, ng,
+                          w->x.as<uint32_t>(), tstride)))
+    return rc;
+  HIP_TRY(launch_scatter_rows(w->x.as<uint32_t>(), tstride, w->sk_inv.as<uint32_t>(), ng, mc.S, O, ostride, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (timed) {
+    float label_ms = 0;
+    HIP_TRY(hipEventElapsedTime(&label_ms, w->ev[2], w->ev[3]));
+    std::lock_guard<std::mutex> lk(ctx->tmu);
+    ctx->total_ms += label_ms;
+  }
+  hfirst->swap(first);
+  hcounts->swap(sizes);
+  return DDS_OK;
+}
+
+// what both string-keyed entry points refuse before they look at a column
+int fold_by_str_args(const dds_col* col, const dds_strtab* by, const size_t* ngroups) {
+  if (!col || !by || !ngroups) return fail(DDS_E_ARG, "bad arguments");
+  return DDS_OK;
+}
+
+// the checks that need the column and the table; the caller holds both locks
+int fold_by_str_rows(const dds_col* col, const StrKeys& K, const uint64_t* mask, size_t mask_words) {
+  if (K.ctx != col->ctx) return fail(DDS_E_ARG, "the column and the table must belong to one context");
+  if (K.count != col->count) return fail(DDS_E_ARG, "the string table and the folded column differ in rows");
+  if (mask && mask_words < (K.count + 63) / 64) return fail(DDS_E_ARG, "mask needs ceil(count / 64) words");
+  if (K.count > (size_t)0xFFFFFFFFu) return fail(DDS_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
+  return DDS_OK;
+}
+
+void give_first(const std::vector<uint32_t>& f, const std::vector<uint32_t>& c, uint64_t* first_rows,
+                uint64_t* counts) {
+  if (first_rows)
+    for (size_t g = 0; g < f.size(); ++g) first_rows[g] = f[g];
+  give_counts(c, counts);
 }
 
 void give_keys(const std::vector<int64_t>& k, const std::vector<uint32_t>& c, int64_t* keys, uint64_t* counts) {
@@ -649,6 +811,84 @@ int dds_col_fold_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, s
     if (*ngroups == 0) return DDS_OK;
     if ((rc = rows_to_be(w, wl.st, mc, w->x.as<uint32_t>(), stride, *ngroups, false, out, mc.bytes))) return rc;
     give_keys(k, c, keys, counts);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_fold_by_str(dds_col* col, dds_strtab* by, size_t position, const uint64_t* mask, size_t mask_words,
+                        dds_col* out, uint64_t* first_rows, uint64_t* counts, size_t cap, size_t* ngroups,
+                        int* passes) {
+  try {
+    int rc = fold_by_str_args(col, by, ngroups);
+    if (rc) return rc;
+    *ngroups = 0;
+    if (passes) *passes = 0;
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    if (out == col) return fail(DDS_E_ARG, "out and the source column must differ");
+    ColWriteLock lk(out, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lr(col->mu, std::defer_lock);  // `col` and `by` are only read
+    std::shared_lock<std::shared_mutex> lb(strtab_mutex(by), std::defer_lock);
+    std::lock(lk.lk, lr, lb);
+    lk.touches_from(out->count);  // an append
+    if (col->ctx != out->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
+    if (bn::cmp(out->mc->N, col->mc->N) != 0 || out->mc->S != col->mc->S || out->mc->W != col->mc->W)
+      return fail(DDS_E_ARG, "columns must be over the same modulus");
+    const StrKeys K = strtab_keys(by);
+    if ((rc = fold_by_str_rows(col, K, mask, mask_words))) return rc;
+    if (K.count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    std::vector<uint32_t> f, c;
+    // rows past the count: nothing is published unless the whole call succeeds
+    auto dest = [&](size_t ng, uint32_t** O, size_t* ostride) {
+      if (ng > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
+      *O = out->d + out->count;
+      *ostride = out->stride;
+      return (int)DDS_OK;
+    };
+    if ((rc = fold_by_str_device(col, K, position, wl.w, wl.st, mask, cap, ngroups, passes, &f, &c, dest))) return rc;
+    out->count += *ngroups;
+    give_first(f, c, first_rows, counts);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
+
+int dds_col_fold_by_str_be(dds_col* col, dds_strtab* by, size_t position, const uint64_t* mask, size_t mask_words,
+                           uint8_t* out, uint64_t* first_rows, uint64_t* counts, size_t cap, size_t* ngroups,
+                           int* passes) {
+  try {
+    int rc = fold_by_str_args(col, by, ngroups);
+    if (rc) return rc;
+    *ngroups = 0;
+    if (passes) *passes = 0;
+    if (cap && !out) return fail(DDS_E_ARG, "bad arguments");
+    std::shared_lock<std::shared_mutex> lr(col->mu, std::defer_lock);
+    std::shared_lock<std::shared_mutex> lb(strtab_mutex(by), std::defer_lock);
+    std::lock(lr, lb);
+    ModConsts& mc = *col->mc;
+    const StrKeys K = strtab_keys(by);
+    if ((rc = fold_by_str_rows(col, K, mask, mask_words))) return rc;
+    if (K.count == 0) return DDS_OK;
+    WorkerLease wl(col->ctx);
+    if ((rc = wl.acquire())) return rc;
+    Worker* w = wl.w;
+    std::vector<uint32_t> f, c;
+    size_t stride = 0;
+    auto dest = [&](size_t ng, uint32_t** O, size_t* ostride) {
+      stride = round_up(ng, 64);  // check_rows(mc, ng) has passed
+      GRP_ALLOC(w->x2.ensure((size_t)mc.S * stride * 4));
+      *O = w->x2.as<uint32_t>();
+      *ostride = stride;
+      return (int)DDS_OK;
+    };
+    if ((rc = fold_by_str_device(col, K, position, w, wl.st, mask, cap, ngroups, passes, &f, &c, dest))) return rc;
+    if (*ngroups == 0) return DDS_OK;
+    if ((rc = rows_to_be(w, wl.st, mc, w->x2.as<uint32_t>(), stride, *ngroups, false, out, mc.bytes))) return rc;
+    give_first(f, c, first_rows, counts);
     return DDS_OK;
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");

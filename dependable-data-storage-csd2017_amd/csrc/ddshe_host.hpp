@@ -114,6 +114,9 @@ struct Worker {
   // dense ranks (ddshe_rank.hip): the sorted permutation, the tiles' head counts, the segment starts, the distinct
   // keys, the labels, and for dds_col_fold_by_ope the valid bytes and the caller's row mask
   DevBuf rk_perm, rk_sums, rk_start, rk_keys, rk_lab, rk_valid, rk_mask;
+  // dds_col_fold_by_str (ddshe_strkey.hip): the rows' digest keys, the verification's mismatch counter, the groups
+  // in first-row order and its inverse
+  DevBuf sk_key, sk_ctr, sk_ord, sk_inv;
   // running totals (ddshe_scan.cpp): the upper levels' planes (totals, carries), the call's row ids
   DevBuf scan_lv, scan_ids;
   // segmented scan: the head-byte planes (two sets for a window's two scans), the call's segment starts, the
@@ -786,6 +789,21 @@ struct OpeKeys {
 };
 std::shared_mutex& opecol_mutex(dds_opecol* col);
 OpeKeys opecol_keys(const dds_opecol* col);
+// What dds_col_fold_by_str (ddshe_groups.cpp) reads of a resident string table (ddshe_strtab.cpp): strtab_mutex is
+// the table's lock; strtab_keys, called with it held (shared), gives the device layout of ddshe_strscan.hip: the
+// rows' current versions and live bytes, and the element heap (nheap elements, nchars bytes).
+struct StrKeys {
+  dds_ctx* ctx = nullptr;
+  size_t count = 0;
+  const uint64_t* d_row_beg = nullptr;
+  const uint32_t* d_row_len = nullptr;
+  const uint8_t* d_live = nullptr;
+  const uint64_t* d_elem_off = nullptr;
+  const uint8_t* d_chars = nullptr;
+  size_t nheap = 0, nchars = 0;
+};
+std::shared_mutex& strtab_mutex(dds_strtab* tab);
+StrKeys strtab_keys(const dds_strtab* tab);
 int combine_partials(dds_ctx* ctx, const uint8_t* mod_be, size_t mod_bytes, const uint32_t* h_parts,
                      const uint32_t* d_parts, const uint64_t* rows, size_t nparts, uint8_t* out, size_t out_cap,
                      size_t* out_len);

@@ -344,6 +344,35 @@ hipError_t launch_ope_rank(const int64_t* col, const uint8_t* valid, const uint3
 hipError_t launch_rank_counts(const uint32_t* starts, size_t ngroups, size_t n, uint32_t* counts, hipStream_t st);
 hipError_t launch_by_valid(const uint8_t* cls, uint32_t hold, const uint8_t* bdead, const uint8_t* clive,
                            const uint64_t* mask, size_t n, uint8_t* valid, hipStream_t st);
+// GROUP BY a string column (ddshe_strkey.hip, ddshe_strkey.hpp) over the string table's device arrays (nheap
+// elements, nchars bytes; n = the table's rows, in [1, 2^32 - 1]). launch_strkey: valid[r] = row r takes part (live
+// in the table, clive[r] != 0 and bit r of mask, both nullable: no such condition, and the row holds `position`),
+// key[r] = the top `bits` bits of the element's digest under `salt`, 0 for a row that takes no part.
+// launch_strkey_verify: perm = launch_ope_order's ascending permutation of key / valid; *mismatches (a device word,
+// zeroed here) <- the participating slots that are no segment head and whose element differs from the slot
+// before's. launch_strkey_order: first[g] = perm[starts[g]] for the ngroups segments launch_ope_rank found, as the
+// int64 keys of the sort that orders the groups. launch_strkey_inv: inv[ord[g]] = g.
+hipError_t launch_strkey(const uint64_t* row_beg, const uint32_t* row_len, const uint8_t* live, const uint64_t* elem_off,
+                         const uint8_t* chars, uint64_t nheap, uint64_t nchars, uint64_t position, const uint8_t* clive,
+                         const uint64_t* mask, size_t n, uint64_t salt, int bits, uint8_t* valid, int64_t* key,
+                         hipStream_t st);
+hipError_t launch_strkey_verify(const uint32_t* perm, const uint8_t* valid, const int64_t* key, size_t n,
+                                const uint64_t* row_beg, const uint32_t* row_len, const uint64_t* elem_off,
+                                const uint8_t* chars, uint64_t nheap, uint64_t nchars, uint64_t position,
+                                uint32_t* mismatches, hipStream_t st);
+hipError_t launch_strkey_order(const uint32_t* perm, const uint32_t* starts, size_t ngroups, size_t n, int64_t* first,
+                               hipStream_t st);
+hipError_t launch_strkey_inv(const uint32_t* ord, size_t ngroups, uint32_t* inv, hipStream_t st);
+// The text of element `position` of the table rows ids[0..n): lens[i] and present[i] (0 and 0 for a row that is out
+// of range, dead or lacks the position); then, one wave per element, its bytes to out[offs[i] .. offs[i + 1]) for
+// the offsets the host summed from those lengths (out_bytes = offs[n]; n <= 2^26 - 1).
+hipError_t launch_str_elem_len(const uint32_t* ids, size_t n, const uint64_t* row_beg, const uint32_t* row_len,
+                               const uint8_t* live, const uint64_t* elem_off, uint64_t nheap, uint64_t nchars,
+                               size_t nrows, uint64_t position, uint64_t* lens, uint8_t* present, hipStream_t st);
+hipError_t launch_str_read(const uint32_t* ids, size_t n, const uint8_t* present, const uint64_t* row_beg,
+                           const uint32_t* row_len, const uint64_t* elem_off, const uint8_t* chars, uint64_t nheap,
+                           uint64_t nchars, size_t nrows, uint64_t position, const uint64_t* offs, uint64_t out_bytes,
+                           uint8_t* out, hipStream_t st);
 // deterministic-equality scans (ddshe_strscan.hip)
 // 64-bit digest of an element string (FNV-1a over the bytes, splitmix finaliser); identical on
 // host (needles) and device (table). The table keeps its top 16 bits as a per-element fingerprint

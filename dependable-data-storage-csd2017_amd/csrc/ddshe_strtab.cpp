@@ -424,7 +424,87 @@ int str_scan(dds_strtab* t, size_t row0, size_t nrows, const char* const* values
 }
 }  // namespace
 
+namespace ddshe {
+namespace host {
+std::shared_mutex& strtab_mutex(dds_strtab* tab) { return tab->mu; }
+StrKeys strtab_keys(const dds_strtab* tab) {
+  StrKeys k;
+  k.ctx = tab->ctx;
+  k.count = tab->nrows;
+  k.d_row_beg = tab->row_beg;
+  k.d_row_len = tab->row_len;
+  k.d_live = tab->live;
+  k.d_elem_off = tab->elem_off;
+  k.d_chars = tab->chars;
+  k.nheap = tab->nheap;
+  k.nchars = tab->nchars;
+  return k;
+}
+}  // namespace host
+}  // namespace ddshe
+
 extern "C" {
+
+int dds_strtab_read_elems(dds_strtab* tab, const uint64_t* rows, size_t n, size_t position, char* chars,
+                          size_t chars_cap, uint64_t* offsets, uint8_t* present, size_t* need) {
+  try {
+    if (!tab || !offsets || (n && !rows)) return fail(DDS_E_ARG, "bad arguments");
+    if (need) *need = 0;
+    if (n > (size_t)0x3FFFFFFu) return fail(DDS_E_UNSUPPORTED, "more than 2^26 - 1 elements in one call");
+    std::shared_lock<std::shared_mutex> lk(tab->mu);
+    for (size_t i = 0; i < n; ++i)
+      if (rows[i] >= tab->nrows) return fail(DDS_E_ARG, "row id " + std::to_string(rows[i]) + " out of range");
+    if (n == 0) {
+      offsets[0] = 0;
+      return DDS_OK;
+    }
+    WorkerLease wl(tab->ctx);
+    int rc;
+    if ((rc = wl.acquire())) return rc;
+    Worker* w = wl.w;
+    hipStream_t st = wl.st;
+    // ids up; lengths and present bytes back through the pinned read-back buffer
+    std::vector<uint32_t> ids(rows, rows + n);  // < nrows < 2^32
+    HIP_TRY(w->ids.ensure(n * 4));
+    HIP_TRY(w->misc.ensure(n * 9));
+    HIP_TRY(w->misc2.ensure((n + 1) * 8));
+    HIP_TRY(w->hbig.ensure(n * 9));
+    uint64_t* d_lens = w->misc.as<uint64_t>();
+    uint8_t* d_pres = reinterpret_cast<uint8_t*>(d_lens + n);
+    HIP_TRY(hipMemcpyAsync(w->ids.p, ids.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(launch_str_elem_len(w->ids.as<uint32_t>(), n, tab->row_beg, tab->row_len, tab->live, tab->elem_off,
+                                tab->nheap, tab->nchars, tab->nrows, position, d_lens, d_pres, st));
+    HIP_TRY(hipMemcpyAsync(w->hbig.p, d_lens, n * 9, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const uint64_t* hl = (const uint64_t*)w->hbig.p;
+    const uint8_t* hp = (const uint8_t*)(hl + n);
+    std::vector<uint64_t> off(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+      if (hl[i] > tab->nchars) return fail(DDS_E_HIP, "element length out of range");
+      off[i + 1] = off[i] + hl[i];
+    }
+    const uint64_t total = off[n];
+    if (need) *need = (size_t)total;
+    if (total > chars_cap)
+      return fail(DDS_E_BUFSIZE, std::to_string(total) + " bytes of text, room for " + std::to_string(chars_cap));
+    if (total && !chars) return fail(DDS_E_ARG, "bad arguments");
+    const std::vector<uint8_t> pres(hp, hp + n);  // the pinned buffer is reused below
+    if (total) {
+      HIP_TRY(w->out.ensure(total));
+      HIP_TRY(hipMemcpyAsync(w->misc2.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice, st));
+      HIP_TRY(launch_str_read(w->ids.as<uint32_t>(), n, d_pres, tab->row_beg, tab->row_len, tab->elem_off, tab->chars,
+                              tab->nheap, tab->nchars, tab->nrows, position, w->misc2.as<uint64_t>(), total,
+                              w->out.as<uint8_t>(), st));
+      HIP_TRY(hipMemcpyAsync(chars, w->out.p, total, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));  // off and the caller's buffer are free again
+    }
+    std::copy(off.begin(), off.end(), offsets);
+    if (present) std::copy(pres.begin(), pres.end(), present);
+    return DDS_OK;
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
 
 int dds_strtab_create(dds_ctx* ctx, const char* chars, const uint64_t* elem_offsets, size_t nelems,
                       const uint64_t* row_offsets, size_t nrows, dds_strtab** out) {

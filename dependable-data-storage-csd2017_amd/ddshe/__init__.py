@@ -77,6 +77,7 @@ EXPORTS = [
     "dds_col_append_scan", "dds_col_scan_be", "dds_scan_plan", "dds_col_scan_by_ope", "dds_col_scan_by_ope_be",
     "dds_col_append_scan_seg", "dds_col_scan_seg_be", "dds_segscan_plan", "dds_col_scan_part_by_ope",
     "dds_col_scan_part_by_ope_be", "dds_col_append_window", "dds_col_window_be", "dds_window_plan",
+    "dds_col_fold_by_str", "dds_col_fold_by_str_be", "dds_strtab_read_elems",
 ]
 
 _u8p = C.POINTER(C.c_uint8)
@@ -197,6 +198,11 @@ _sig("dds_ope_rank", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, _u32p, _i
 _sig("dds_ope_rank_device", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _sz, C.c_void_p, C.c_void_p, C.c_void_p, _szp)
 _sig("dds_col_fold_by_ope", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, C.c_void_p, _i64p, _u64p, _sz, _szp)
 _sig("dds_col_fold_by_ope_be", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, _u8p, _i64p, _u64p, _sz, _szp)
+_sig("dds_col_fold_by_str", C.c_int, C.c_void_p, C.c_void_p, _sz, _u64p, _sz, C.c_void_p, _u64p, _u64p, _sz, _szp,
+     C.POINTER(C.c_int))
+_sig("dds_col_fold_by_str_be", C.c_int, C.c_void_p, C.c_void_p, _sz, _u64p, _sz, _u8p, _u64p, _u64p, _sz, _szp,
+     C.POINTER(C.c_int))
+_sig("dds_strtab_read_elems", C.c_int, C.c_void_p, _u64p, _sz, _sz, C.c_void_p, _sz, _u64p, _u8p, _szp)
 _sig("dds_col_append_scan", C.c_int, C.c_void_p, C.c_void_p, _u64p, _sz, _sz, C.c_int)
 _sig("dds_col_scan_be", C.c_int, C.c_void_p, _u64p, _sz, _sz, C.c_int, _u8p)
 _sig("dds_scan_plan", C.c_int, _sz, C.POINTER(C.c_int), C.POINTER(C.c_int), _u64p, _u64p)
@@ -1125,6 +1131,52 @@ class Column(_Mutable):
         _check(rc, "dds_col_fold_by_ope")
         return keys, counts
 
+    @staticmethod
+    def _by_str(tab: "StrTable", mask, cap, call):
+        """call(mask pointer, mask words, first_rows, counts, cap, ngroups, passes) -> status, with room for `cap`
+        groups (default: up to 4,096); a result with more groups is asked for again at the size the engine reports
+        (DDS_E_BUFSIZE wrote nothing). Returns (status, first_rows, counts, passes)."""
+        words = None if mask is None else np.ascontiguousarray(mask, dtype=np.uint64)
+        cap = max(1, min(tab.nrows, 4096)) if cap is None else cap
+        ng, passes = C.c_size_t(), C.c_int()
+        while True:
+            first, counts = np.empty(max(1, cap), dtype=np.uint64), np.empty(max(1, cap), dtype=np.uint64)
+            rc = call(None if words is None else words.ctypes.data_as(_u64p), 0 if words is None else len(words),
+                      first.ctypes.data_as(_u64p), counts.ctypes.data_as(_u64p), cap, C.byref(ng), C.byref(passes))
+            if rc != DDS_E_BUFSIZE or ng.value <= cap:
+                n = ng.value if rc == DDS_OK else 0
+                return rc, first[:n], counts[:n], passes.value
+            cap = ng.value
+
+    def fold_by_str(self, tab: "StrTable", position: int, mask=None, cap: int | None = None):
+        """dds_col_fold_by_str_be: SELECT text, SUM(x) GROUP BY text with the keys in element `position` of the
+        resident string table `tab` (row r of the column and of the table is the same stored set). mask: uint64
+        row-mask words as OpeColumn.search_mask returns them (a WHERE), or None. Returns (first_rows, values, counts,
+        passes): per distinct text in order of first occurrence the smallest participating row id holding it
+        (StrTable.read_elems gives the texts), the product mod N of its rows as a canonical residue, how many rows
+        that were, and the labelling passes the call ran (1 unless a digest collision was met)."""
+        out = None
+
+        def call(m, mw, first, counts, cap, ng, passes):
+            nonlocal out
+            out = (C.c_uint8 * (self.mb * max(1, cap)))()
+            return _lib.dds_col_fold_by_str_be(self._h, tab._h, position, m, mw, out, first, counts, cap, ng, passes)
+
+        rc, first, counts, passes = self._by_str(tab, mask, cap, call)
+        _check(rc, "dds_col_fold_by_str_be")
+        raw = C.string_at(C.addressof(out), self.mb * len(first))
+        vals = [int.from_bytes(raw[g * self.mb:(g + 1) * self.mb], "big") for g in range(len(first))]
+        return first, vals, counts, passes
+
+    def append_fold_by_str(self, src: "Column", tab: "StrTable", position: int, mask=None, cap: int | None = None):
+        """dds_col_fold_by_str: the same values of src's rows appended to this column, group g at the old
+        len(self) + g, canonical and live; returns (first_rows, counts, passes)."""
+        rc, first, counts, passes = self._by_str(tab, mask, cap, lambda m, mw, first, counts, cap, ng, passes:
+                                                 _lib.dds_col_fold_by_str(src._h, tab._h, position, m, mw, self._h,
+                                                                          first, counts, cap, ng, passes))
+        _check(rc, "dds_col_fold_by_str")
+        return first, counts, passes
+
     def _scan_args(self, row_ids, first, count):
         if row_ids is None:
             return None, len(self) - first if count is None else count
@@ -1640,6 +1692,24 @@ class StrTable:
             self.close()
         except Exception:
             pass
+
+    def read_elems(self, rows, position: int) -> list:
+        """dds_strtab_read_elems: the text of element `position` of the listed rows (ids may repeat) as bytes, None
+        for a row that is dead or lacks the position."""
+        ids = np.ascontiguousarray(rows, dtype=np.uint64)
+        n = len(ids)
+        offs, pres, need = np.zeros(n + 1, dtype=np.uint64), np.zeros(max(1, n), dtype=np.uint8), C.c_size_t()
+        cap = max(64, 32 * n)
+        while True:
+            buf = C.create_string_buffer(cap)
+            rc = _lib.dds_strtab_read_elems(self._h, ids.ctypes.data_as(_u64p), n, position, buf, cap,
+                                            offs.ctypes.data_as(_u64p), pres.ctypes.data_as(_u8p), C.byref(need))
+            if rc != DDS_E_BUFSIZE or need.value <= cap:
+                break
+            cap = need.value
+        _check(rc, "dds_strtab_read_elems")
+        raw = buf.raw
+        return [raw[int(offs[i]):int(offs[i + 1])] if pres[i] else None for i in range(n)]
 
     def search_eq(self, position: int, value, negate: bool = False) -> np.ndarray:
         v = element_text(value).encode()

@@ -415,6 +415,42 @@ class ResidentStore:
             raise ServerError(f"InvalidKeySpecException: {e}") from e
         return self._fold_by(self.by_pos_mult.get(position), by_position, n)
 
+    def _fold_by_str(self, c: _CipherColumn | None, by_position: int, modulus: int, where) -> dict[str, str]:
+        """_fold_by with the labels made on the GPU from the resident string table (dds_col_fold_by_str_be): the same
+        rows, groups and 500 / 404 answers, no per-row host work; `where` as _fold_by_ope's. The key texts come back
+        from the table (dds_strtab_read_elems of each group's first row)."""
+        if c is None or modulus != c.modulus:
+            raise ServerError("no resident column at this position under this modulus")
+        if self.tab is None:
+            raise ServerError("no resident string table")
+        if c.bad:
+            raise ServerError("NumberFormatException: a qualifying element is not an integer")
+        if c.nlive == 0:
+            raise NotFound()
+        try:
+            first, vals, _, _ = c.col.fold_by_str(self.tab, by_position, self._where_mask(where))
+            texts = self.tab.read_elems(first, by_position)
+        except DDSError as e:
+            raise ServerError(str(e)) from e
+        return {t.decode(): str(v) for t, v in zip(texts, vals)}
+
+    def sum_all_by_str(self, position: int, by_position: int, nsqr: str, where=None) -> dict[str, str]:
+        """sum_all_by with the grouping done on the GPU from the resident string table: the same result, groups in
+        order of first occurrence; where: (route, position, value) as sum_all_by_ope's. Raises ServerError when no
+        string table is resident."""
+        x = _bigint(nsqr)
+        if x is None:
+            raise ServerError("NumberFormatException: nsqr")
+        return self._fold_by_str(self.by_pos_sum.get(position), by_position, x, where)
+
+    def mult_all_by_str(self, position: int, by_position: int, pubkey: str, where=None) -> dict[str, str]:
+        """MultAll per group, as sum_all_by_str, under the modulus of pubkey."""
+        try:
+            n = rsa_modulus(pubkey)
+        except ValueError as e:
+            raise ServerError(f"InvalidKeySpecException: {e}") from e
+        return self._fold_by_str(self.by_pos_mult.get(position), by_position, n, where)
+
     def _fold_by_ope(self, c: _CipherColumn | None, by_position: int, modulus: int, where,
                      descending: bool | None = None) -> dict[int, str]:
         """the grouped fold of column c keyed by the resident OPE column at by_position: the rows its resident

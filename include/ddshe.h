@@ -698,6 +698,48 @@ int dds_col_fold_by_ope(dds_col* col, dds_opecol* by, const uint64_t* mask, size
 int dds_col_fold_by_ope_be(dds_col* col, dds_opecol* by, const uint64_t* mask, size_t mask_words, uint8_t* out,
                            int64_t* keys, uint64_t* counts, size_t cap, size_t* ngroups);
 
+/* ---- GROUP BY a string column: the grouped fold keyed by a resident dds_strtab ----------
+ * SELECT text, SUM(x) [WHERE ...] GROUP BY text: row r of `col` and row r of `by` are the same stored set
+ * (dds_strtab_rows(by) != dds_col_count(col), or different contexts: DDS_E_ARG). Row r takes part iff it is live in
+ * col, live in by, its current version holds the position (length > position: the grouped folds' guard, not
+ * SearchEq's strict one) and, when mask is not NULL, bit r % 64 of mask[r / 64] is set (the layout and the
+ * DDS_E_ARG on too few words of dds_opecol_search_mask). Rows are one group iff the bytes of their element
+ * `position` are equal, length and content: "7" and the Int 7 are one group, "07" another. Group g is the g-th
+ * distinct text by the smallest participating row id that holds it: the order of first occurrence, which depends
+ * on the data only. first_rows[g] = that row id (the key's text: the caller's own store, or dds_strtab_read_elems),
+ * counts[g] >= 1 (both nullable, `cap` entries each), the value the product mod N of the group's rows in ascending
+ * row order as a canonical residue, as dds_col_fold_groups gives it. No participating row: DDS_OK with
+ * *ngroups = 0. *ngroups > cap: DDS_E_BUFSIZE with *ngroups the count required, nothing written or appended.
+ * The grouping is exact, not probabilistic. The table keeps 16 fingerprint bits per element, so the key is
+ * recomputed from the bytes: a salted 64-bit digest per row, the stable sort and the rank kernels of
+ * dds_col_fold_by_ope, and then a verification that compares every row of a segment of equal digests with the row
+ * before it, byte for byte. No mismatch proves every segment is one string (equality is transitive) and distinct
+ * segments are distinct strings (their digests differ). A mismatch is a digest collision (about d^2 / 2^65 for d
+ * distinct texts): the pass is repeated under the next salt, at most 4 passes; *passes (nullable) = the passes
+ * run, set whenever the labelling ran. A mismatch in the last pass: DDS_E_UNSUPPORTED, nothing written. Nothing per
+ * row crosses to the device but the optional mask. Locking, threading and timing as dds_col_fold_by_ope (col and
+ * by shared, out exclusive, acquired together; the labelling adds to total_ms, the fold levels to fold_ms); a
+ * workspace allocation that fails: DDS_E_NOMEM. A NULL col, by or ngroups: DDS_E_ARG before any GPU work.
+ * DDSHE_STRKEY_BITS=<1..64> (a test switch, read on every call) truncates the first pass's key to that many bits. */
+/* Column form: appends *ngroups canonical, live rows to out (same modulus and context, out != col, else DDS_E_ARG;
+ * capacity exceeded: DDS_E_ARG), group g at old count + g; nothing is published unless the whole call succeeds. */
+int dds_col_fold_by_str(dds_col* col, dds_strtab* by, size_t position, const uint64_t* mask, size_t mask_words,
+                        dds_col* out, uint64_t* first_rows, uint64_t* counts, size_t cap, size_t* ngroups,
+                        int* passes);
+/* The same values as big-endian rows of the column's modulus width: out holds cap * mod_bytes bytes, *ngroups rows
+ * are written (out may be NULL when cap == 0). */
+int dds_col_fold_by_str_be(dds_col* col, dds_strtab* by, size_t position, const uint64_t* mask, size_t mask_words,
+                           uint8_t* out, uint64_t* first_rows, uint64_t* counts, size_t cap, size_t* ngroups,
+                           int* passes);
+/* The text of element `position` of the table rows rows[0..n) (ids may repeat), in the batch layout the table
+ * ingests: the bytes back to back in chars, offsets[n + 1] with offsets[0] = 0. present[i] (nullable) = 0 for a row
+ * that is dead or lacks the position (length <= position); such a row contributes empty text. A row id out of
+ * range, a NULL tab or offsets, a NULL rows with n > 0: DDS_E_ARG. More than chars_cap bytes: DDS_E_BUFSIZE with
+ * *need (nullable) the bytes required, nothing written; on success *need = the bytes written. The lengths come
+ * back first, the host sums them, and one kernel copies the elements, one wave each. The table is locked shared. */
+int dds_strtab_read_elems(dds_strtab* tab, const uint64_t* rows, size_t n, size_t position, char* chars,
+                          size_t chars_cap, uint64_t* offsets, uint8_t* present, size_t* need);
+
 /* ---- running totals: prefix products of resident rows ----------
  * The scan beside the folds (reductions) and the row-wise calls (maps): out row j = x_0 * ... * x_j mod N over the
  * call's rows taken in order, Enc(m_0 + ... + m_j) for a Paillier column, the running product for an RSA one; with
