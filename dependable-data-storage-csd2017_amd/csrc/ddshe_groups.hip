@@ -1,4 +1,4 @@
-// Grouping of the grouped fold (dds_col_fold_groups, host side in ddshe_groups.cpp) and the launchers of its
+// Grouping of the grouped fold (dds_col_fold_groups, host side in ddshe_groups_host.cpp) and the launchers of its
 // segmented fold (k_grp_fold of ddshe_groups.hpp): a counting sort of the call's live items by label.
 //
 //   k_grp_count:     cnt[g] = live items with label g. Up to kGroupsLdsLabels groups a block counts its tile in LDS

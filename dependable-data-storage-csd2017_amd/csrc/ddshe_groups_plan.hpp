@@ -1,4 +1,4 @@
-// Plan of the grouped fold (dds_col_fold_groups, host side in ddshe_groups.cpp, kernels in ddshe_groups.hpp): the
+// Plan of the grouped fold (dds_col_fold_groups, host side in ddshe_groups_host.cpp, kernels in ddshe_groups.hpp): the
 // call's live rows, sorted into one segment per group, are folded kGroupsFan rows per lane group and level, every
 // segment at once. From the per-group counts the plan gives, per level, one descriptor per chunk (where its inputs
 // lie, how many, where the result goes, which constant it takes), the rows of the two scratch buffers the levels

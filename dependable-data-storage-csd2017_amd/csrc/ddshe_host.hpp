@@ -1,6 +1,6 @@
 // Host-side internals of the C-ABI (shared by ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp, ddshe_opecol.cpp,
-// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp, ddshe_groups.cpp,
-// ddshe_scan.cpp):
+// ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime_host.cpp, ddshe_linear.cpp, ddshe_groups_host.cpp,
+// ddshe_keyed.cpp, ddshe_scan_host.cpp):
 // contexts, stream/buffer pools, per-modulus Montgomery constants, device columns and the
 // orchestration helpers around the HIP kernels. Not part of the public ABI (include/ddshe.h).
 #pragma once
@@ -39,6 +39,27 @@ int fail(int code, const std::string& msg);
     hipError_t e_ = (expr);                                                                       \
     if (e_ != hipSuccess) return fail(DDS_E_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
   } while (0)
+
+// a device allocation that fails is the caller's DDS_E_NOMEM ("what": whose workspace), anything else a HIP error
+#define DEV_ALLOC(expr, what)                                                                      \
+  do {                                                                                             \
+    hipError_t e_ = (expr);                                                                        \
+    if (e_ == hipErrorOutOfMemory) {                                                               \
+      (void)hipGetLastError();                                                                     \
+      return fail(DDS_E_NOMEM, what);                                                              \
+    }                                                                                              \
+    if (e_ != hipSuccess) return fail(DDS_E_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
+  } while (0)
+
+// an entry point's body with a failed host allocation made its status
+template <class F>
+int no_throw(F body) {
+  try {
+    return body();
+  } catch (const std::bad_alloc&) {
+    return fail(DDS_E_NOMEM, "host allocation");
+  }
+}
 
 struct DevBuf {
   void* p = nullptr;
@@ -108,7 +129,7 @@ struct Worker {
   DevBuf wf_w, wf_ids, wf_hist, wf_cnt, wf_list;
   // batched inversion (inv_device): the prefix products of a chunk's rows, the upper levels' planes
   DevBuf inv_pfx, inv_lv;
-  // grouped fold (ddshe_groups.cpp): the call's labels and row ids, group sizes, scan cursors and tile sums, the
+  // grouped fold (ddshe_groups_host.cpp): the call's labels and row ids, group sizes, scan cursors and tile sums, the
   // sorted id list, the levels' chunk descriptors, the two level buffers
   DevBuf gp_lab, gp_ids, gp_cnt, gp_cur, gp_sums, gp_list, gp_desc, gp_buf[2];
   // dense ranks (ddshe_rank.hip): the sorted permutation, the tiles' head counts, the segment starts, the distinct
@@ -117,7 +138,7 @@ struct Worker {
   // dds_col_fold_by_str (ddshe_strkey.hip): the rows' digest keys, the verification's mismatch counter, the groups
   // in first-row order and its inverse
   DevBuf sk_key, sk_ctr, sk_ord, sk_inv;
-  // running totals (ddshe_scan.cpp): the upper levels' planes (totals, carries), the call's row ids
+  // running totals (ddshe_scan_host.cpp): the upper levels' planes (totals, carries), the call's row ids
   DevBuf scan_lv, scan_ids;
   // segmented scan: the head-byte planes (two sets for a window's two scans), the call's segment starts, the
   // windows' suffix products
@@ -304,7 +325,7 @@ struct dds_ctx {
     bool owned = false;  // allocated by dds_host_alloc (hipHostFree), else registered caller memory
   };
   std::map<uintptr_t, HostReg> host_regs;
-  // prime search (ddshe_prime.cpp): the odd primes below 2^16, built and uploaded by the first call (under prmu)
+  // prime search (ddshe_prime_host.cpp): the odd primes below 2^16, built and uploaded by the first call (under prmu)
   std::mutex prmu;
   ddshe::host::DevBuf prime_tab;
   uint32_t prime_count = 0;
@@ -405,6 +426,20 @@ struct ColWriteLock {
     }
   }
 };
+
+// two resident columns of one call (of any kind) must live in the same context
+inline int one_context(const dds_ctx* a, const dds_ctx* b) {
+  if (a != b) return fail(DDS_E_ARG, "columns must belong to one context");
+  return DDS_OK;
+}
+
+// the checks of an appending call on `out` and one column it reads; the caller holds both locks
+inline int append_pair_ok(const dds_col* out, const dds_col* in) {
+  if (int rc = one_context(in->ctx, out->ctx)) return rc;
+  if (bn::cmp(out->mc->N, in->mc->N) != 0 || out->mc->S != in->mc->S || out->mc->W != in->mc->W)
+    return fail(DDS_E_ARG, "columns must be over the same modulus");
+  return DDS_OK;
+}
 
 // Coalescing queue of the pairwise routes for one modulus: a caller queues its pair; whoever finds
 // a batch slot free becomes a leader and runs one k_pairs launch over everything queued so far (group
@@ -652,7 +687,7 @@ int exprows_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const
 // written. Synchronises the stream. With the context's timing on, the kernels' device time goes to total_ms.
 int inv_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* d_x, size_t xstride,
                const uint32_t* d_num, size_t nstride, size_t count, uint32_t* d_out, size_t ostride, size_t* bad_row);
-// Running totals on the device (ddshe_scan.cpp, ddshe_scan_plan.hpp): row j of O <- x_0 · … · x_j mod N, canonical,
+// Running totals on the device (ddshe_scan_host.cpp, ddshe_scan_plan.hpp): row j of O <- x_0 · … · x_j mod N, canonical,
 // over the call's n >= 1 rows of X (xrows rows at xstride, below 2N): x_j = row d_list[j] (a device list of n ids,
 // each below xrows), or row first + j when d_list is null. suffix: row j of O <- x_j · … · x_(n-1); with a list the
 // caller passes it reversed (d_list[j] = the id of input n - 1 - j). O (n rows at ostride) must not overlap X.
@@ -660,9 +695,24 @@ int inv_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uin
 // plan's products to fold_modmuls. A workspace allocation that fails: DDS_E_NOMEM.
 int scan_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const uint32_t* X, size_t xstride, size_t xrows,
                 const uint32_t* d_list, size_t first, size_t n, bool suffix, uint32_t* O, size_t ostride);
-// the modulus' table R^k mod N, k = 0 .. F + 1 (mc.dgtab), built on first use (ddshe_groups.cpp)
+// the modulus' table R^k mod N, k = 0 .. F + 1 (mc.dgtab), built on first use (ddshe_groups_host.cpp)
 int scan_table(ModConsts& mc);
-// The segmented scan on the device (ddshe_scan.cpp; SegScanPlan of ddshe_scan_plan.hpp): scan_device's rows, the
+// DEV_ALLOC's texts of the grouped and keyed folds and of the scans
+constexpr const char* kGroupsWs = "device workspace of the grouped fold";
+constexpr const char* kScanWs = "device workspace of the scan";
+// group sizes into a caller's nullable uint64 array
+inline void give_counts(const std::vector<uint32_t>& c, uint64_t* counts) {
+  if (counts)
+    for (size_t g = 0; g < c.size(); ++g) counts[g] = c[g];
+}
+// The segmented fold (ddshe_groups_host.cpp): segment g of d_list[0..cap) holds counts[g] row ids of the column,
+// segment after segment; row g of O (stride ostride, not overlapping the column) <- the canonical product of segment
+// g's rows, the literal 1 for an empty one (d_cnt: the counts on the device, read only then). The caller holds
+// col->mu and has built scan_table. Synchronises the stream. With timing on, the levels add to fold_ms,
+// fold_launches and fold_modmuls.
+int fold_segments(dds_col* col, Worker* w, hipStream_t st, const uint32_t* d_list, size_t cap, const uint32_t* counts,
+                  const uint32_t* d_cnt, size_t ngroups, uint32_t* O, size_t ostride);
+// The segmented scan on the device (ddshe_scan_host.cpp; SegScanPlan of ddshe_scan_plan.hpp): scan_device's rows, the
 // product restarting at every head. heads: the head positions of the order scanned (seg_heads), from which the plan
 // counts the products; the head bytes themselves are made on the device from d_starts (nseg ascending starts, `base`
 // subtracted from each; reversed when suffix). d_list is read as given, or backwards with list_rev (a suffix scan
@@ -773,7 +823,7 @@ int col_write_prepare(dds_col* col, const uint64_t* ids, size_t n, const uint8_t
                       const char* chars, const uint64_t* offsets, RowWrite* plan);
 int col_write_commit(dds_col* col, RowWrite& plan);
 int col_set_live(dds_col* col, const uint64_t* ids, size_t n, const uint8_t* live);
-// What dds_col_fold_by_ope (ddshe_groups.cpp) reads of a resident OPE column (ddshe_opecol.cpp): opecol_mutex is
+// What dds_col_fold_by_ope (ddshe_keyed.cpp) reads of a resident OPE column (ddshe_opecol.cpp): opecol_mutex is
 // the column's lock; opecol_keys, called with it held (shared), gives the device arrays (d_dead null: no removed
 // set yet), the bounds of the stored values in unsigned order (launch_ope_order's ubounds) and the live holders
 // whose element is malformed / outside int64.
@@ -789,7 +839,7 @@ struct OpeKeys {
 };
 std::shared_mutex& opecol_mutex(dds_opecol* col);
 OpeKeys opecol_keys(const dds_opecol* col);
-// What dds_col_fold_by_str (ddshe_groups.cpp) reads of a resident string table (ddshe_strtab.cpp): strtab_mutex is
+// What dds_col_fold_by_str (ddshe_keyed.cpp) reads of a resident string table (ddshe_strtab.cpp): strtab_mutex is
 // the table's lock; strtab_keys, called with it held (shared), gives the device layout of ddshe_strscan.hip: the
 // rows' current versions and live bytes, and the element heap (nheap elements, nchars bytes).
 struct StrKeys {

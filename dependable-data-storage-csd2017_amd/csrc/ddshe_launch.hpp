@@ -1,6 +1,6 @@
 // Internal launcher interface between the C-ABI's host code (ddshe_capi.cpp, ddshe_paillier.cpp, ddshe_rsa.cpp,
-// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime.cpp, ddshe_linear.cpp,
-// ddshe_groups.cpp) and the HIP kernels.
+// ddshe_opecol.cpp, ddshe_strtab.cpp, ddshe_mctx.cpp, ddshe_pairs.cpp, ddshe_prime_host.cpp, ddshe_linear.cpp,
+// ddshe_groups_host.cpp, ddshe_keyed.cpp, ddshe_scan_host.cpp) and the HIP kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

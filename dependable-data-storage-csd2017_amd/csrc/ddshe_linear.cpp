@@ -7,8 +7,8 @@
 // them (include/ddshe.h: dds_modexp_rows, dds_col_append_pow, dds_exprows_plan, dds_col_fold_weighted[_dec],
 // dds_fold_weighted_plan, dds_modinv_rows, dds_col_append_inv, dds_col_append_quot, dds_col_append_mul).
 #include "ddshe_exprows_plan.hpp"
-#include "ddshe_host.hpp"
 #include "ddshe_inv_plan.hpp"
+#include "ddshe_sink.hpp"
 #include "ddshe_wfold_plan.hpp"
 
 using namespace ddshe;
@@ -168,12 +168,8 @@ int col_append_rowwise(dds_col* out, dds_col* a, size_t a_first, dds_col* b, siz
     std::lock(lk.lk, lb);
   }
   lk.touches_from(out->count);  // an append
-  for (dds_col* src : {a, b}) {
-    if (!src) continue;
-    if (src->ctx != out->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
-    if (bn::cmp(out->mc->N, src->mc->N) != 0 || out->mc->S != src->mc->S || out->mc->W != src->mc->W)
-      return fail(DDS_E_ARG, "columns must be over the same modulus");
-  }
+  for (dds_col* src : {a, b})
+    if (int rc = src ? append_pair_ok(out, src) : (int)DDS_OK) return rc;
   if (b_first > b->count || count > b->count - b_first) return fail(DDS_E_ARG, "rows out of range");
   if (a && (a_first > a->count || count > a->count - a_first)) return fail(DDS_E_ARG, "rows out of range");
   if (count > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
@@ -404,25 +400,23 @@ int dds_col_append_pow(dds_col* out, dds_col* in, size_t first, size_t count, co
   try {
     if (!out || !in || (count && !exps)) return fail(DDS_E_ARG, "bad arguments");
     if (out == in) return fail(DDS_E_ARG, "out and in columns must differ");
-    ColWriteLock lk(out, std::defer_lock);
+    AppendSink sink(out);
     std::shared_lock<std::shared_mutex> lr(in->mu, std::defer_lock);  // `in` is only read
-    std::lock(lk.lk, lr);
-    lk.touches_from(out->count);  // an append
-    if (bn::cmp(out->mc->N, in->mc->N) != 0 || out->mc->S != in->mc->S || out->mc->W != in->mc->W)
-      return fail(DDS_E_ARG, "columns must be over the same modulus");
-    if (first > in->count || count > in->count - first) return fail(DDS_E_ARG, "rows out of range");
-    if (count > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
-    if (count == 0) return DDS_OK;
-    WorkerLease wl(out->ctx);
     int rc;
+    if ((rc = sink.open(in, lr))) return rc;
+    if (first > in->count || count > in->count - first) return fail(DDS_E_ARG, "rows out of range");
+    if ((rc = sink.check(count)) || count == 0) return rc;
+    WorkerLease wl(out->ctx);
     if ((rc = wl.acquire())) return rc;
     if ((rc = upload_exps(wl.w, wl.st, exps, count))) return rc;
+    uint32_t* O = nullptr;
+    size_t ostride = 0;
+    if ((rc = sink.dest(wl.w, count, &O, &ostride))) return rc;
     // canonical residues straight into the new rows; the device function synchronises
     if ((rc = exprows_device(out->ctx, wl.w, wl.st, *out->mc, in->d + first, in->stride, wl.w->exps.as<uint64_t>(),
-                             max_exp_bits(exps, count), count, out->d + out->count, out->stride)))
+                             max_exp_bits(exps, count), count, O, ostride)))
       return rc;
-    out->count += count;
-    return DDS_OK;
+    return sink.commit(wl.w, wl.st, count);
   } catch (const std::bad_alloc&) {
     return fail(DDS_E_NOMEM, "host allocation");
   }

@@ -1,6 +1,6 @@
 // Prime search on the GPU (gfx950): the strong probable-prime test at one candidate per lane, the small-prime
 // sieve over windows of odd candidates, and the kernels that move candidates in and out. The hot path of
-// HomoAdd.generateKey / HomoMult.generateKey (utils/SJHomoLibProvider.scala:33-40; host side in ddshe_prime.cpp).
+// HomoAdd.generateKey / HomoMult.generateKey (utils/SJHomoLibProvider.scala:33-40; host side in ddshe_prime_host.cpp).
 //
 // k_strong1<S1, W, Base2>: lane t tests N = row idx[t / rounds] of Ncol (limb-transposed, Ncol[l * nstride + row],
 // S1 limbs of W bits, odd, >= 3, bits(N) <= W S1 - 2 so that 4N <= R1 = 2^(W S1)) to one base and stores

@@ -1,4 +1,4 @@
-// Host arithmetic of the prime search and the key generators (ddshe_prime.cpp): the limb classes of the strong
+// Host arithmetic of the prime search and the key generators (ddshe_prime_host.cpp): the limb classes of the strong
 // test, the table of sieve primes, the default window, the seeded draws and tags of the key generators, and the
 // per-key finishing steps (HomoAdd.generateKey / HomoMult.generateKey, utils/SJHomoLibProvider.scala:33-40).
 // No HIP: prime_check.cpp compiles it alone and checks it against bn:: arithmetic.

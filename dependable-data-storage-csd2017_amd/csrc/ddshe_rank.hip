@@ -1,5 +1,5 @@
 // Dense ranks of an int64 key column (dds_ope_rank, and the grouping of dds_col_fold_by_ope; host side in
-// ddshe_groups.cpp). The stable ascending sort of ddshe_sort.hip (launch_ope_order) gives perm: the invalid rows
+// ddshe_keyed.cpp). The stable ascending sort of ddshe_sort.hip (launch_ope_order) gives perm: the invalid rows
 // first, then the valid ones by key, equal keys in row order. Slot j of perm is a HEAD when it holds a valid row
 // and is the first such slot or its key differs from the slot before; the exclusive scan of the head flags numbers
 // the distinct keys in ascending signed order:

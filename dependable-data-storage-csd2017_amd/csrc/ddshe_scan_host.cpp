@@ -1,30 +1,19 @@
 // Running totals on the GPU: out row j = the product mod N of the call's rows 0..j, in order (include/ddshe.h:
-// dds_col_append_scan, dds_col_scan_be, dds_scan_plan; dds_col_scan_by_ope[_be] are in ddshe_groups.cpp, next to the
-// labelling and the segmented fold they reuse, and run scan_device over the group totals). The levels are
+// dds_col_append_scan, dds_col_scan_be, dds_scan_plan; dds_col_scan_by_ope[_be] are in ddshe_keyed.cpp, next to the
+// labelling they reuse, and run scan_device over the group totals). The levels are
 // ddshe_scan_plan.hpp's: chunk totals up, the carries of the top level in one lane group, the carries down, the
 // totals at the rows (kernels in ddshe_scan.hpp). The host inverts nothing and combines nothing: 2 * levels + 1
 // launches and one synchronisation. The opaque rows only: it reads col->d and neither uses nor touches the digit
 // mirror.
 // Also here: the segmented scan, whose running product restarts at every segment start (dds_col_append_scan_seg,
 // dds_col_scan_seg_be, dds_segscan_plan; seg_scan_device also serves dds_col_scan_part_by_ope[_be] of
-// ddshe_groups.cpp), and the moving windows built on it (dds_col_append_window, dds_col_window_be, dds_window_plan):
+// ddshe_keyed.cpp), and the moving windows built on it (dds_col_append_window, dds_col_window_be, dds_window_plan):
 // SegScanPlan and WindowPlan of ddshe_scan_plan.hpp, the k_seg_* and k_win_* kernels.
-#include "ddshe_host.hpp"
 #include "ddshe_scan_plan.hpp"
+#include "ddshe_sink.hpp"
 
 using namespace ddshe;
 using namespace ddshe::host;
-
-// a device allocation that fails is the caller's DDS_E_NOMEM, anything else a HIP error
-#define SCAN_ALLOC(expr)                                                                           \
-  do {                                                                                             \
-    hipError_t e_ = (expr);                                                                        \
-    if (e_ == hipErrorOutOfMemory) {                                                               \
-      (void)hipGetLastError();                                                                     \
-      return fail(DDS_E_NOMEM, "device workspace of the scan");                                    \
-    }                                                                                              \
-    if (e_ != hipSuccess) return fail(DDS_E_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-  } while (0)
 
 namespace ddshe {
 namespace host {
@@ -39,7 +28,7 @@ int scan_device(dds_ctx* ctx, Worker* w, hipStream_t st, ModConsts& mc, const ui
   const size_t top = pl.top();
   for (size_t i = 1; i <= top; ++i)
     if (pl.stride[i] > max_stride(S)) return fail(DDS_E_UNSUPPORTED, "level plane exceeds the row limit of this modulus");
-  if (pl.scratch_rows) SCAN_ALLOC(w->scan_lv.ensure(pl.scratch_rows * (size_t)S * 4));
+  if (pl.scratch_rows) DEV_ALLOC(w->scan_lv.ensure(pl.scratch_rows * (size_t)S * 4), kScanWs);
   uint32_t* lv = w->scan_lv.as<uint32_t>();
   auto T = [&](size_t i) { return lv + pl.t_off(i, S); };
   auto C = [&](size_t i) { return lv + pl.c_off(i, S); };
@@ -82,8 +71,8 @@ int seg_scan_room(Worker* w, const ModConsts& mc, const SegScanPlan& pl, size_t 
   for (size_t i = 1; i <= lv.top(); ++i)
     if (lv.stride[i] > max_stride(mc.S))
       return fail(DDS_E_UNSUPPORTED, "level plane exceeds the row limit of this modulus");
-  if (lv.scratch_rows) SCAN_ALLOC(w->scan_lv.ensure(lv.scratch_rows * (size_t)mc.S * 4));
-  SCAN_ALLOC(w->seg_h.ensure(sets * pl.hbytes));
+  if (lv.scratch_rows) DEV_ALLOC(w->scan_lv.ensure(lv.scratch_rows * (size_t)mc.S * 4), kScanWs);
+  DEV_ALLOC(w->seg_h.ensure(sets * pl.hbytes), kScanWs);
   return DDS_OK;
 }
 
@@ -192,7 +181,7 @@ int scan_col(dds_col* in, Worker* w, hipStream_t st, const uint64_t* row_ids, si
   if (row_ids) {
     ids32.resize(n);  // < count <= max_stride < 2^32
     for (size_t i = 0; i < n; ++i) ids32[i] = (uint32_t)row_ids[suffix ? n - 1 - i : i];
-    SCAN_ALLOC(w->scan_ids.ensure(n * 4));
+    DEV_ALLOC(w->scan_ids.ensure(n * 4), kScanWs);
     HIP_TRY(hipMemcpyAsync(w->scan_ids.p, ids32.data(), n * 4, hipMemcpyHostToDevice, st));
     d_list = w->scan_ids.as<uint32_t>();
   }
@@ -222,11 +211,11 @@ int seg_scan_col(dds_col* in, Worker* w, hipStream_t st, const uint64_t* row_ids
                  const uint64_t* seg_starts, size_t nseg, bool suffix, uint32_t* O, size_t ostride) {
   std::vector<uint32_t> ids32, st32(seg_starts, seg_starts + nseg);  // starts < n < 2^32
   const uint32_t* d_list = nullptr;
-  SCAN_ALLOC(w->seg_starts.ensure(nseg * 4));
+  DEV_ALLOC(w->seg_starts.ensure(nseg * 4), kScanWs);
   if (row_ids) {
     ids32.resize(n);  // < count <= max_stride < 2^32
     for (size_t i = 0; i < n; ++i) ids32[i] = (uint32_t)row_ids[suffix ? n - 1 - i : i];
-    SCAN_ALLOC(w->scan_ids.ensure(n * 4));
+    DEV_ALLOC(w->scan_ids.ensure(n * 4), kScanWs);
     HIP_TRY(hipMemcpyAsync(w->scan_ids.p, ids32.data(), n * 4, hipMemcpyHostToDevice, st));
     d_list = w->scan_ids.as<uint32_t>();
   }
@@ -256,13 +245,13 @@ int window_col(dds_col* in, Worker* w, hipStream_t st, const uint64_t* row_ids, 
   const size_t sstride = round_up(n, 64);
   if (wp.joined) {
     if ((rc = check_rows(mc, n))) return rc;
-    SCAN_ALLOC(w->seg_sx.ensure((size_t)S * sstride * 4));
+    DEV_ALLOC(w->seg_sx.ensure((size_t)S * sstride * 4), kScanWs);
   }
   std::vector<uint32_t> ids32;
   const uint32_t* d_list = nullptr;
   if (row_ids) {
     ids32.assign(row_ids, row_ids + n);  // < count <= max_stride < 2^32
-    SCAN_ALLOC(w->scan_ids.ensure(n * 4));
+    DEV_ALLOC(w->scan_ids.ensure(n * 4), kScanWs);
     HIP_TRY(hipMemcpyAsync(w->scan_ids.p, ids32.data(), n * 4, hipMemcpyHostToDevice, st));
     d_list = w->scan_ids.as<uint32_t>();
   }
@@ -303,12 +292,37 @@ int window_args(const dds_col* in, size_t n, size_t w) {
   return DDS_OK;
 }
 
-// the checks of an appending call on its two columns; the caller holds both locks
-int append_pair_ok(const dds_col* out, const dds_col* in) {
-  if (in->ctx != out->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
-  if (bn::cmp(out->mc->N, in->mc->N) != 0 || out->mc->S != in->mc->S || out->mc->W != in->mc->W)
-    return fail(DDS_E_ARG, "columns must be over the same modulus");
-  return DDS_OK;
+// The six positional entry points behind their own argument checks and locks: the call's n >= 1 rows to the sink,
+// made by run(w, st, O, ostride): scan_col, seg_scan_col or window_col over `in`.
+template <class Sink, class Run>
+int scan_to(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, Sink& sink, Run run) {
+  int rc;
+  if ((rc = scan_rows(in, row_ids, first, n))) return rc;
+  if ((rc = sink.check(n))) return rc;
+  WorkerLease wl(in->ctx);
+  if ((rc = wl.acquire())) return rc;
+  uint32_t* O = nullptr;
+  size_t ostride = 0;
+  if ((rc = sink.dest(wl.w, n, &O, &ostride))) return rc;
+  if ((rc = run(wl.w, wl.st, O, ostride))) return rc;
+  return sink.commit(wl.w, wl.st, n);
+}
+
+// the appending form: out's lock with a shared one on `in`, which is only read
+template <class Run>
+int scan_append(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n, Run run) {
+  AppendSink sink(out);
+  std::shared_lock<std::shared_mutex> lr(in->mu, std::defer_lock);
+  if (int rc = sink.open(in, lr)) return rc;
+  return scan_to(in, row_ids, first, n, sink, run);
+}
+
+// the bytes form
+template <class Run>
+int scan_bytes(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, uint8_t* out, Run run) {
+  std::shared_lock<std::shared_mutex> lk(in->mu);
+  BytesSink sink{*in->mc, &Worker::x, kScanWs, out};
+  return scan_to(in, row_ids, first, n, sink, run);
 }
 
 }  // namespace
@@ -354,107 +368,6 @@ int dds_window_plan(size_t n, size_t w, int* fan, int* levels, uint64_t* product
   }
 }
 
-int dds_col_append_scan_seg(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n,
-                            const uint64_t* seg_starts, size_t nseg, int suffix) {
-  try {
-    if (!out) return fail(DDS_E_ARG, "bad arguments");
-    int rc = scan_args(in, n);
-    if (rc) return rc;
-    if (out == in) return fail(DDS_E_ARG, "out and the source column must differ");
-    if (n == 0) return DDS_OK;
-    if ((rc = seg_starts_ok(seg_starts, nseg, n))) return rc;
-    ColWriteLock lk(out, std::defer_lock);
-    std::shared_lock<std::shared_mutex> lr(in->mu, std::defer_lock);  // `in` is only read
-    std::lock(lk.lk, lr);
-    lk.touches_from(out->count);  // an append
-    if ((rc = append_pair_ok(out, in))) return rc;
-    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
-    if (n > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
-    WorkerLease wl(in->ctx);
-    if ((rc = wl.acquire())) return rc;
-    // rows past the count: nothing is published unless the call succeeds
-    if ((rc = seg_scan_col(in, wl.w, wl.st, row_ids, first, n, seg_starts, nseg, suffix != 0, out->d + out->count,
-                           out->stride)))
-      return rc;
-    out->count += n;
-    return DDS_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
-int dds_col_scan_seg_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, const uint64_t* seg_starts,
-                        size_t nseg, int suffix, uint8_t* out) {
-  try {
-    int rc = scan_args(in, n);
-    if (rc) return rc;
-    if (n == 0) return DDS_OK;  // nothing to write: out may be NULL
-    if (!out) return fail(DDS_E_ARG, "bad arguments");
-    if ((rc = seg_starts_ok(seg_starts, nseg, n))) return rc;
-    std::shared_lock<std::shared_mutex> lk(in->mu);
-    ModConsts& mc = *in->mc;
-    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
-    if ((rc = check_rows(mc, n))) return rc;
-    WorkerLease wl(in->ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    const size_t stride = round_up(n, 64);
-    SCAN_ALLOC(w->x.ensure((size_t)mc.S * stride * 4));
-    if ((rc = seg_scan_col(in, w, wl.st, row_ids, first, n, seg_starts, nseg, suffix != 0, w->x.as<uint32_t>(), stride)))
-      return rc;
-    return rows_to_be(w, wl.st, mc, w->x.as<uint32_t>(), stride, n, false, out, mc.bytes);
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
-int dds_col_append_window(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n, size_t w) {
-  try {
-    if (!out) return fail(DDS_E_ARG, "bad arguments");
-    int rc = window_args(in, n, w);
-    if (rc) return rc;
-    if (out == in) return fail(DDS_E_ARG, "out and the source column must differ");
-    if (n == 0) return DDS_OK;
-    ColWriteLock lk(out, std::defer_lock);
-    std::shared_lock<std::shared_mutex> lr(in->mu, std::defer_lock);  // `in` is only read
-    std::lock(lk.lk, lr);
-    lk.touches_from(out->count);  // an append
-    if ((rc = append_pair_ok(out, in))) return rc;
-    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
-    if (n > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
-    WorkerLease wl(in->ctx);
-    if ((rc = wl.acquire())) return rc;
-    // rows past the count: nothing is published unless the call succeeds
-    if ((rc = window_col(in, wl.w, wl.st, row_ids, first, n, w, out->d + out->count, out->stride))) return rc;
-    out->count += n;
-    return DDS_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
-int dds_col_window_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, size_t w, uint8_t* out) {
-  try {
-    int rc = window_args(in, n, w);
-    if (rc) return rc;
-    if (n == 0) return DDS_OK;  // nothing to write: out may be NULL
-    if (!out) return fail(DDS_E_ARG, "bad arguments");
-    std::shared_lock<std::shared_mutex> lk(in->mu);
-    ModConsts& mc = *in->mc;
-    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
-    if ((rc = check_rows(mc, n))) return rc;
-    WorkerLease wl(in->ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* wk = wl.w;
-    const size_t stride = round_up(n, 64);
-    SCAN_ALLOC(wk->x.ensure((size_t)mc.S * stride * 4));
-    if ((rc = window_col(in, wk, wl.st, row_ids, first, n, w, wk->x.as<uint32_t>(), stride))) return rc;
-    return rows_to_be(wk, wl.st, mc, wk->x.as<uint32_t>(), stride, n, false, out, mc.bytes);
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
-}
-
 int dds_scan_plan(size_t n, int* fan, int* levels, uint64_t* products, uint64_t* workspace_rows) {
   try {
     if (n > (size_t)0xFFFFFFFFu) return fail(DDS_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
@@ -470,52 +383,73 @@ int dds_scan_plan(size_t n, int* fan, int* levels, uint64_t* products, uint64_t*
 }
 
 int dds_col_append_scan(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n, int suffix) {
-  try {
-    if (!out) return fail(DDS_E_ARG, "bad arguments");
-    int rc = scan_args(in, n);
-    if (rc) return rc;
-    if (out == in) return fail(DDS_E_ARG, "out and the source column must differ");
-    if (n == 0) return DDS_OK;
-    ColWriteLock lk(out, std::defer_lock);
-    std::shared_lock<std::shared_mutex> lr(in->mu, std::defer_lock);  // `in` is only read
-    std::lock(lk.lk, lr);
-    lk.touches_from(out->count);  // an append
-    if (in->ctx != out->ctx) return fail(DDS_E_ARG, "columns must belong to one context");
-    if (bn::cmp(out->mc->N, in->mc->N) != 0 || out->mc->S != in->mc->S || out->mc->W != in->mc->W)
-      return fail(DDS_E_ARG, "columns must be over the same modulus");
-    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
-    if (n > out->capacity - out->count) return fail(DDS_E_ARG, "column capacity exceeded");
-    WorkerLease wl(in->ctx);
-    if ((rc = wl.acquire())) return rc;
-    // rows past the count: nothing is published unless the call succeeds
-    if ((rc = scan_col(in, wl.w, wl.st, row_ids, first, n, suffix != 0, out->d + out->count, out->stride))) return rc;
-    out->count += n;
-    return DDS_OK;
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
+  return no_throw([&]() -> int {
+    int rc;
+    if ((rc = AppendSink::given(out)) || (rc = scan_args(in, n)) || (rc = AppendSink::apart(out, in)) || n == 0)
+      return rc;
+    return scan_append(out, in, row_ids, first, n, [&](Worker* w, hipStream_t st, uint32_t* O, size_t ostride) {
+      return scan_col(in, w, st, row_ids, first, n, suffix != 0, O, ostride);
+    });
+  });
 }
 
 int dds_col_scan_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, int suffix, uint8_t* out) {
-  try {
-    int rc = scan_args(in, n);
-    if (rc) return rc;
-    if (n == 0) return DDS_OK;  // nothing to write: out may be NULL
+  return no_throw([&]() -> int {
+    const int rc = scan_args(in, n);
+    if (rc || n == 0) return rc;  // nothing to write: out may be NULL
     if (!out) return fail(DDS_E_ARG, "bad arguments");
-    std::shared_lock<std::shared_mutex> lk(in->mu);
-    ModConsts& mc = *in->mc;
-    if ((rc = scan_rows(in, row_ids, first, n))) return rc;
-    if ((rc = check_rows(mc, n))) return rc;
-    WorkerLease wl(in->ctx);
-    if ((rc = wl.acquire())) return rc;
-    Worker* w = wl.w;
-    const size_t stride = round_up(n, 64);
-    SCAN_ALLOC(w->x.ensure((size_t)mc.S * stride * 4));
-    if ((rc = scan_col(in, w, wl.st, row_ids, first, n, suffix != 0, w->x.as<uint32_t>(), stride))) return rc;
-    return rows_to_be(w, wl.st, mc, w->x.as<uint32_t>(), stride, n, false, out, mc.bytes);
-  } catch (const std::bad_alloc&) {
-    return fail(DDS_E_NOMEM, "host allocation");
-  }
+    return scan_bytes(in, row_ids, first, n, out, [&](Worker* w, hipStream_t st, uint32_t* O, size_t ostride) {
+      return scan_col(in, w, st, row_ids, first, n, suffix != 0, O, ostride);
+    });
+  });
+}
+
+int dds_col_append_scan_seg(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n,
+                            const uint64_t* seg_starts, size_t nseg, int suffix) {
+  return no_throw([&]() -> int {
+    int rc;
+    if ((rc = AppendSink::given(out)) || (rc = scan_args(in, n)) || (rc = AppendSink::apart(out, in)) || n == 0)
+      return rc;
+    if ((rc = seg_starts_ok(seg_starts, nseg, n))) return rc;
+    return scan_append(out, in, row_ids, first, n, [&](Worker* w, hipStream_t st, uint32_t* O, size_t ostride) {
+      return seg_scan_col(in, w, st, row_ids, first, n, seg_starts, nseg, suffix != 0, O, ostride);
+    });
+  });
+}
+
+int dds_col_scan_seg_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, const uint64_t* seg_starts,
+                        size_t nseg, int suffix, uint8_t* out) {
+  return no_throw([&]() -> int {
+    int rc = scan_args(in, n);
+    if (rc || n == 0) return rc;  // nothing to write: out may be NULL
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    if ((rc = seg_starts_ok(seg_starts, nseg, n))) return rc;
+    return scan_bytes(in, row_ids, first, n, out, [&](Worker* w, hipStream_t st, uint32_t* O, size_t ostride) {
+      return seg_scan_col(in, w, st, row_ids, first, n, seg_starts, nseg, suffix != 0, O, ostride);
+    });
+  });
+}
+
+int dds_col_append_window(dds_col* out, dds_col* in, const uint64_t* row_ids, size_t first, size_t n, size_t w) {
+  return no_throw([&]() -> int {
+    int rc;
+    if ((rc = AppendSink::given(out)) || (rc = window_args(in, n, w)) || (rc = AppendSink::apart(out, in)) || n == 0)
+      return rc;
+    return scan_append(out, in, row_ids, first, n, [&](Worker* wk, hipStream_t st, uint32_t* O, size_t ostride) {
+      return window_col(in, wk, st, row_ids, first, n, w, O, ostride);
+    });
+  });
+}
+
+int dds_col_window_be(dds_col* in, const uint64_t* row_ids, size_t first, size_t n, size_t w, uint8_t* out) {
+  return no_throw([&]() -> int {
+    const int rc = window_args(in, n, w);
+    if (rc || n == 0) return rc;  // nothing to write: out may be NULL
+    if (!out) return fail(DDS_E_ARG, "bad arguments");
+    return scan_bytes(in, row_ids, first, n, out, [&](Worker* wk, hipStream_t st, uint32_t* O, size_t ostride) {
+      return window_col(in, wk, st, row_ids, first, n, w, O, ostride);
+    });
+  });
 }
 
 }  // extern "C"

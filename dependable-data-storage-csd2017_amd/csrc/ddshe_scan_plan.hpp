@@ -1,5 +1,5 @@
 // Level plan of the running totals (dds_col_append_scan, dds_col_scan_be, dds_col_scan_by_ope; host side in
-// ddshe_scan.cpp, kernels in ddshe_scan.hpp): out_j = x_0 · … · x_j mod N over the call's n rows, taken in order.
+// ddshe_scan_host.cpp, kernels in ddshe_scan.hpp): out_j = x_0 · … · x_j mod N over the call's n rows, taken in order.
 // Level 0 is the inputs; every level is cut into CONTIGUOUS chunks of kScanFan rows, one lane group per chunk, and
 // the chunk totals of level i are the rows of level i + 1, until at most kScanFan rows remain (level top). The plan
 // gives the rows of every level, where a level's two planes (totals T, carries C) lie in the scratch, the launches

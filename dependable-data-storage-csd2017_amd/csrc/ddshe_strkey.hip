@@ -1,4 +1,4 @@
-// GROUP BY a string column (dds_col_fold_by_str[_be]; host side in ddshe_groups.cpp) and the text egress of the
+// GROUP BY a string column (dds_col_fold_by_str[_be]; host side in ddshe_keyed.cpp) and the text egress of the
 // group keys (dds_strtab_read_elems; host side in ddshe_strtab.cpp). The labelling never moves a byte of text to the
 // host: over the string table's device layout (ddshe_strscan.hip: row_beg, row_len, live, elem_off, chars)
 //   k_strkey:        one thread per row: the sort's valid byte (ddshe_strkey.hpp: strkey_takes_part) and its int64

@@ -1,5 +1,5 @@
 // CPU check of the grouped fold's plan and Montgomery exponents (ddshe_groups_plan.hpp as fold_groups_device of
-// ddshe_groups.cpp drives k_grp_fold of ddshe_groups.hpp). No HIP, value level: for each lane-group shape's
+// ddshe_groups_host.cpp drives k_grp_fold of ddshe_groups.hpp). No HIP, value level: for each lane-group shape's
 // R = 2^(W·S) a call with groups of 0, 1, 2, F - 1, F, F + 1, 2F, F² - 1, F², F² + 1 and 2F² + 3 rows is laid out by
 // GroupsPlan and replayed chunk by chunk with the Montgomery product the kernels compute (check_util.hpp's MontR)
 // and the table R^k mod N, applying the kernel's own descriptor guards, and every group's value is compared with

@@ -1,5 +1,5 @@
 // CPU check of the running totals' plan and Montgomery exponents (ddshe_scan_plan.hpp as scan_device of
-// ddshe_scan.cpp drives the kernels of ddshe_scan.hpp). No HIP, value level: for each lane-group shape's
+// ddshe_scan_host.cpp drives the kernels of ddshe_scan.hpp). No HIP, value level: for each lane-group shape's
 // R = 2^(W·S) calls of 0, 1, 2, F - 1, F, F + 1, 2F, F² - 1, F², F² + 1 and 2F² + 3 rows (F³ + 1, three levels of
 // totals, at S = 40 only) are laid out by ScanPlan and replayed launch by launch and chunk by chunk with the
 // Montgomery product the kernels compute (check_util.hpp's MontR; a value-level restatement, so the lazy 64-bit

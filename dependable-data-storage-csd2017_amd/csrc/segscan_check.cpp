@@ -1,5 +1,5 @@
 // CPU check of the segmented scan's plan and Montgomery exponents (SegScanPlan and WindowPlan of
-// ddshe_scan_plan.hpp as seg_scan_device and window_col of ddshe_scan.cpp drive the k_seg_* kernels of
+// ddshe_scan_plan.hpp as seg_scan_device and window_col of ddshe_scan_host.cpp drive the k_seg_* kernels of
 // ddshe_scan.hpp). No HIP, value level, as scan_check.cpp: for each lane-group shape's R = 2^(W·S) the plan of a
 // call is replayed launch by launch and chunk by chunk with check_util.hpp's MontR and the table R^k mod N, with the
 // kernels' own addressing (a range, the reversed range, a list, the list read backwards, the reversed list the host

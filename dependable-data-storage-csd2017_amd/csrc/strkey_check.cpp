@@ -1,5 +1,5 @@
 // CPU check of the grouping by strings (dds_col_fold_by_str: label_by_str and fold_by_str_device of
-// ddshe_groups.cpp driving the kernels of ddshe_strkey.hip). No device code: a model of the passes built on the
+// ddshe_keyed.cpp driving the kernels of ddshe_strkey.hip). No device code: a model of the passes built on the
 // shared primitives of ddshe_strkey.hpp -- the salted digest truncated to the pass's bits, a stable sort of the
 // participating rows by it, the segment heads, the adjacent verification, the salt loop, the groups ordered by their
 // first rows -- against a std::map<std::string, ...> grouping of the same rows, over seeded tables with empty
